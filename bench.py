@@ -19,8 +19,19 @@ epsilon = 10.  N > 1, two ways:
                 BASELINE configs[2] is `--gpus 4 --mode shard --reads 1000000 --ref-len 250000000`.
 
 Prints ONE JSON line on rank 0 (contract in the task statement), including `roofline` for the dominant
-kernel (the radix scatter of the k-mer sort) and `cpu_baseline` (the compiled reference pagraph, or the
-C oracle when oracle/_ref is absent, on a bounded sample of the same kind of workload).
+kernel (the radix scatter of the k-mer sort, graded with the traffic kept under profiles/).
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints the line.
+`--full` adds everything else the line can carry, each a measurement or check of its own: `cpu_baseline` (the
+compiled reference pagraph, or the C oracle when oracle/_ref is absent, on a bounded sample of the same kind of
+workload, plus the cached whole-workload records), the device k-mer counter checked against the generator's solid
+set (`config.kmer_counter_on_device`), the check of the traversal against its verified answer (KNOWN_PATHS), the
+live file-to-file leg of the default workload and `roofline.traffic` from two rocprofv3 PMC passes of this run.
+
+`--dump-outputs DIR` writes what the last timed step computed (rank 0's block) as DIR/<name>.npy, float32 /
+float64, under 64 MB in all: the build and traversal counts and the output files the traversal wrote (sizes,
+SHA-256 digests and a fixed, seeded sample of their bytes).  The inputs are seeded, so two builds run with the
+same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -207,6 +218,35 @@ def cpu_baseline(k, eps, cov, threads_flag):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+DUMP_SAMPLE_BYTES = 8 << 20  # output-file bytes kept by --dump-outputs: 32 MB as float32
+
+
+def _u64_words(x):
+    """a 64-bit value as four 16-bit words (exact in float64)"""
+    return [float((int(x) >> s) & 0xFFFF) for s in (48, 32, 16, 0)]
+
+
+def dump_outputs(dump_dir, st, ts, out_dir):
+    """What the last timed step computed, as DIR/<name>.npy: the build and traversal counts (the path checksum as four
+    16-bit words) and the files the traversal wrote to out_dir, in name order: their sizes, their SHA-256 digests and
+    their bytes concatenated — all of them up to DUMP_SAMPLE_BYTES, beyond that a fixed, seeded sample of positions."""
+    import hashlib
+    os.makedirs(dump_dir, exist_ok=True)
+    build = [st.n_tuples[0], st.n_tuples[1], st.n_edges[0], st.n_edges[1], st.n_nodes, st.n_pos, st.n_uniq_edges] + list(st.counts())
+    np.save(os.path.join(dump_dir, "build_counts.npy"), np.array([float(v) for v in build], dtype=np.float64))
+    trav = [ts.n_contigs, ts.n_path_nodes, ts.n_path_bases, ts.n_chains_emitted, ts.n_fasta_bases]
+    np.save(os.path.join(dump_dir, "traverse_counts.npy"), np.array([float(v) for v in trav] + _u64_words(ts.path_checksum), dtype=np.float64))
+    names = sorted(f for f in os.listdir(out_dir) if os.path.isfile(os.path.join(out_dir, f)))
+    blobs = [np.fromfile(os.path.join(out_dir, f), dtype=np.uint8) for f in names]
+    np.save(os.path.join(dump_dir, "output_file_sizes.npy"), np.array([b.size for b in blobs], dtype=np.float64))
+    np.save(os.path.join(dump_dir, "output_file_sha256.npy"),
+            np.array([list(hashlib.sha256(b.tobytes()).digest()) for b in blobs], dtype=np.float32).reshape(len(blobs), 32))
+    data = np.concatenate(blobs) if blobs else np.zeros(0, np.uint8)
+    if data.size > DUMP_SAMPLE_BYTES:
+        data = data[np.sort(np.random.default_rng(2024).integers(0, data.size, DUMP_SAMPLE_BYTES))]
+    np.save(os.path.join(dump_dir, "output_bytes.npy"), data.astype(np.float32))
+
+
 # (reads, read_span, ref_len, k, epsilon, seed) -> (path nodes, path checksum) verified against the host walk
 KNOWN_PATHS = {(100_000, 10_000, 50_000_000, 14, 10, 2 + r): v for r, v in enumerate([
     (11924900, "6372939f2ca5e736"), (11927706, "43b7948f5aab8638"), (11923389, "9e3fc4ea4cdd727b"), (11921428, "f6a4b5c0dd98720e"),
@@ -254,12 +294,18 @@ def main():
     ap.add_argument("--build-only", action="store_true", help="diagnostic: skip traversal (NOT a valid bench line)")
     ap.add_argument("--file-to-file", action="store_true",
                     help="also write the workload as TEXT files (/dev/shm, ~25 s) and time the drop-in executable on them, live: "
-                         "config.file_to_file_* (never part of `value`).  On by default for a single-GPU run of the default workload when "
+                         "config.file_to_file_* (never part of `value`).  On by default under --full for a single-GPU run of the default workload when "
                          "/dev/shm has room for the 7 GB of text")
     ap.add_argument("--no-file-to-file", action="store_true")
     ap.add_argument("--no-live-traffic", action="store_true", help="roofline.traffic from the kept profile instead of two rocprofv3 PMC passes in this run")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline, the device k-mer counter check, the known-answer check of the traversal, the live "
+                         "file-to-file leg and the live roofline traffic (the --no-* options above switch single ones off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
-    if not args.file_to_file and not args.no_file_to_file and not args.build_only and int(os.environ.get("WORLD_SIZE", "1")) == 1 and \
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.full and not args.file_to_file and not args.no_file_to_file and not args.build_only and int(os.environ.get("WORLD_SIZE", "1")) == 1 and \
             (args.reads, args.read_span, args.ref_len) == (100_000, 10_000, 50_000_000):
         try:
             st_shm = os.statvfs("/dev/shm")
@@ -306,7 +352,7 @@ def main():
     # Not part of `value` (the reference runs it as a separate program before pagraph); its result must equal the set
     # the generator computed with torch, bit for bit (code k aside: the file header quirk Q1 puts it into the set).
     kc = None
-    if rank == 0 and world == 1 and spec.k <= 14:
+    if args.full and rank == 0 and world == 1 and spec.k <= 14:
         class KmerCountResult(C.Structure):
             _fields_ = [("min_abundance", C.c_uint64), ("n_solid", C.c_uint64), ("n_kmers_counted", C.c_uint64),
                         ("ms_count", C.c_double), ("ms_select", C.c_double)]
@@ -509,7 +555,10 @@ def main():
     finish()  # (the last block's host half: inside the timed region)
     sync()
     dt = time.perf_counter() - t0
-    check_known_answer()  # (outside the timed region)
+    if args.full:
+        check_known_answer()  # (outside the timed region)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, st, ts, out_dir)
     dt_max, total_bases = parallel.aggregate(dist, dt, float(w.n_bases), device="cpu" if one_device else f"cuda:{local}")
     if shard:
         total_bases = float(w.n_bases)  # one block, whatever the number of ranks
@@ -599,7 +648,7 @@ def main():
                          "per_pass": {"kernel": "pagdev::sort_scatter (one radix pass of one stream)", "achieved": achieved, "frac": achieved / HBM_PEAK_GBS,
                                       "records_per_launch": int(st.sort_records), "ms_per_launch": ms_sort, "traffic": traffic}},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline(args.k, args.epsilon, 2, 16)
             except Exception as e:  # the baseline is a report, never a reason to lose the bench line
@@ -692,7 +741,7 @@ def main():
                                                    "stderr_tail": r.stderr[-300:] if r.returncode else ""}
         finally:
             shutil.rmtree(tdir, ignore_errors=True)
-    if rank == 0 and world == 1 and not args.no_live_traffic and not args.build_only:
+    if args.full and rank == 0 and world == 1 and not args.no_live_traffic and not args.build_only:
         # roofline.traffic collected in this run (the bench's own device memory is handed back first: the child builds the same block)
         try:
             if g is not None:

@@ -7,7 +7,7 @@ mkdir -p $out
 t0=$(date +%s)
 timeout 2400 python -m pytest tests -q -m gpu -x --durations=25 > $out/gputest.log 2>&1; tail -40 $out/gputest.log
 echo "suite wall: $(( $(date +%s) - t0 )) s" | tee -a $out/gputest.log
-python bench.py > $out/bench_line.json 2> $out/bench_stderr.log
+python bench.py --full > $out/bench_line.json 2> $out/bench_stderr.log
 tail -c 3000 $out/bench_line.json
 root=$PWD
 cd /tmp && export TMPDIR=/tmp

@@ -10,7 +10,7 @@ t0=$(date +%s)
 timeout 2400 python -m pytest tests -q -m gpu -x --durations=12 > $out/gputest_full_suite.log 2>&1
 echo "suite wall: $(( $(date +%s) - t0 )) s" >> $out/gputest_full_suite.log
 tail -4 $out/gputest_full_suite.log
-python bench.py > $out/bench_line.json 2> $out/bench_stderr.log
+python bench.py --full > $out/bench_line.json 2> $out/bench_stderr.log
 python bench.py --steps 20 --warmup 5 > $out/bench_line_steps20.json 2> $out/bench_stderr_steps20.log
 python - <<'PY'
 import json

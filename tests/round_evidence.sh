@@ -5,7 +5,7 @@ mkdir -p $out
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $out/smoke.log 2>&1; tail -1 $out/smoke.log
 python -m pytest tests -q -m gpu -x > $out/gputest_full_suite.log 2>&1
 tail -3 $out/gputest_full_suite.log
-python bench.py > $out/bench_line.json 2> $out/bench_stderr.log
+python bench.py --full > $out/bench_line.json 2> $out/bench_stderr.log
 tail -c 600 $out/bench_line.json
 root=$PWD
 cd /tmp && export TMPDIR=/tmp

@@ -124,11 +124,11 @@ def test_device_walks_equal_host_walk_on_multi_round_contigs(workdir):
 @pytest.mark.gpu
 def test_bench_line_contract(workdir):
     """bench.py on a small workload: one JSON line with the fields the driver reads, a roofline object for the sort kernel
-    and a cpu_baseline object from the compiled reference (or a stated failure where oracle/_ref is absent)."""
+    and (under --full) a cpu_baseline object from the compiled reference (or a stated failure where oracle/_ref is absent)."""
     import json
     import subprocess
     import sys
-    r = subprocess.run([sys.executable, os.path.join(pagctl.ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--reads", "3000",
+    r = subprocess.run([sys.executable, os.path.join(pagctl.ROOT, "bench.py"), "--full", "--steps", "1", "--warmup", "1", "--reads", "3000",
                         "--ref-len", "3000000"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -143,3 +143,35 @@ def test_bench_line_contract(workdir):
     assert rf["bound"] == "hbm" and rf["unit"] == "GB/s" and rf["peak"] == 8000.0 and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-9
     cb = d["cpu_baseline"]
     assert cb["kind"] in ("reference", "port") and "sample" in cb and "cores" in cb
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_and_dump_outputs(workdir):
+    """A plain bench.py run (no --full): the headline fields, none of the --full legs, `steps` timed steps; --dump-outputs writes
+    float arrays of the last timed step under 64 MB, and a second run with the same arguments dumps the same arrays."""
+    import json
+    import subprocess
+    import sys
+    dumps = []
+    for i in range(2):
+        d = str(workdir / f"bench_dump_{i}")
+        r = subprocess.run([sys.executable, os.path.join(pagctl.ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--reads", "3000",
+                            "--ref-len", "3000000", "--dump-outputs", d], capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in line, key
+        assert line["steps"] == 2 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+        assert "cpu_baseline" not in line and line["config"]["kmer_counter_on_device"] is None
+        files = sorted(os.listdir(d))
+        assert {"build_counts.npy", "traverse_counts.npy", "output_file_sizes.npy", "output_file_sha256.npy", "output_bytes.npy"} <= set(files)
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in files) <= 64 << 20
+        arrs = {f: np.load(os.path.join(d, f)) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert arrs["traverse_counts.npy"][1] == line["config"]["path_nodes"] and arrs["output_bytes.npy"].size > 0
+        dumps.append(arrs)
+    assert dumps[0].keys() == dumps[1].keys()
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
