@@ -10,7 +10,8 @@
 //   kc_count   one wavefront per read: 64 lanes x 16 consecutive k-mer starts per tile, codes from a 64-bit
 //              window of the 2-bit packed read (the same bit tricks as the extraction kernel), atomicAdd per code
 //   kc_hist    histogram of the abundances 0 .. KC_BINS-2, everything larger in the last bin (the rule almost
-//              always stops at a single-digit abundance; the tail is resolved exactly on the host if it does not)
+//              always stops at a single-digit abundance; the tail is resolved exactly on the host if it does not),
+//              and the sum of all abundances (the k-mers counted, exact whatever the bins hold)
 //   kc_select  32 counters -> one bitmap word, population count of the set
 #include <algorithm>
 #include <cstdlib>
@@ -55,14 +56,20 @@ __global__ __launch_bounds__(64) void kc_count(const uint64_t *__restrict__ read
     }
 }
 
-__global__ void kc_hist(const uint32_t *__restrict__ table, uint64_t n, unsigned long long *__restrict__ hist) {
+__global__ void kc_hist(const uint32_t *__restrict__ table, uint64_t n, unsigned long long *__restrict__ hist,
+                        unsigned long long *__restrict__ n_counted) {
     __shared__ uint32_t h[KC_BINS];
     for (uint32_t i = threadIdx.x; i < KC_BINS; i += blockDim.x) h[i] = 0;
     __syncthreads();
+    uint64_t mine = 0;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
         const uint32_t a = table[i];
         atomicAdd(&h[a < KC_BINS - 1 ? a : KC_BINS - 1], 1u);
+        mine += a;
     }
+    uint64_t tot;
+    wave_excl_sum64(mine, &tot);
+    if (lane_id() == 63 && tot) atomicAdd(n_counted, (unsigned long long)tot);
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < KC_BINS; i += blockDim.x)
         if (h[i]) atomicAdd(&hist[i], (unsigned long long)h[i]);
@@ -162,10 +169,11 @@ extern "C" int pag_kmer_count(const pag_seqs *reads, int reads_on_device, uint32
         for (uint32_t sl = 0; sl < (1u << lg); ++sl)
             kc_count<<<dim3(grid), dim3(64), 0, s>>>(d_off, d_len, d_packed, (uint32_t)n_reads, k, table, sl, shift);
     }
-    kc_hist<<<dim3(4096), dim3(256), 0, s>>>(table, n_codes, d_hist);
+    // d_hist: [0, KC_BINS) the histogram, [KC_BINS + 1] the solid count (kc_select), [KC_BINS + 2] the k-mers counted
+    kc_hist<<<dim3(4096), dim3(256), 0, s>>>(table, n_codes, d_hist, d_hist + KC_BINS + 2);
     KC_TRY(hipEventRecord(ev[1], s));
-    std::vector<unsigned long long> hist(KC_BINS);
-    KC_TRY(hipMemcpyAsync(hist.data(), d_hist, KC_BINS * 8, hipMemcpyDeviceToHost, s));
+    std::vector<unsigned long long> hist(KC_BINS + 8);
+    KC_TRY(hipMemcpyAsync(hist.data(), d_hist, (KC_BINS + 8) * 8, hipMemcpyDeviceToHost, s));
     KC_TRY(hipStreamSynchronize(s));
 
     // the reference's rule (kmer_counter.cpp:59-77), same expression in double
@@ -229,9 +237,7 @@ extern "C" int pag_kmer_count(const pag_seqs *reads, int reads_on_device, uint32
         float ms = 0;
         res->min_abundance = min_abundance;
         res->n_solid = ns;
-        uint64_t nk = 0;
-        for (uint32_t a = 0; a < KC_BINS; ++a) nk += (uint64_t)hist[a] * (a < KC_BINS - 1 ? a : 0);
-        res->n_kmers_counted = hist[KC_BINS - 1] ? 0 : nk;  // exact only when no abundance reached the last bin
+        res->n_kmers_counted = hist[KC_BINS + 2];
         hipEventElapsedTime(&ms, ev[0], ev[1]);
         res->ms_count = ms;
         hipEventElapsedTime(&ms, ev[1], ev[2]);

@@ -479,7 +479,7 @@ int pag_cns_consensus(int device, const char *backbone, uint64_t backbone_len, c
 typedef struct pag_kmer_count_result {
     uint64_t min_abundance;
     uint64_t n_solid;
-    uint64_t n_kmers_counted; /* k-mer occurrences (0 if some abundance exceeded the histogram range) */
+    uint64_t n_kmers_counted; /* k-mer occurrences: the sum of all abundances */
     double ms_count, ms_select; /* device time: count + histogram; bitmap */
 } pag_kmer_count_result;
 int pag_kmer_count(const pag_seqs *reads, int reads_on_device, uint32_t k, double threshold, int device, uint32_t *bitmap,

@@ -47,6 +47,7 @@ struct pago_graph {
     uint64_t *dbg_tval, *dbg_eval;
     uint32_t *dbg_tread, *dbg_eread; /* emission position (index into emit_order) of the read that emitted the record */
     uint32_t dbg_cur;
+    uint64_t dbg_max_tile; /* most samples kept in one 1024-position tile of a read strand (the extraction kernel's tile) */
     size_t dbg_nt, dbg_ct, dbg_ne, dbg_ce;
 };
 
@@ -136,6 +137,7 @@ static void node_free(node *nd) {
 int pago_reset(pago_graph *g) {
     for (uint64_t i = 0; i < g->n_solid; ++i) node_free(&g->nodes[i]);
     g->dbg_nt = g->dbg_ne = 0;
+    g->dbg_max_tile = 0;
     return PAG_OK;
 }
 
@@ -159,6 +161,9 @@ int pago_debug_stream_reads(const pago_graph *g, uint32_t *tread, uint32_t *erea
     memcpy(eread, g->dbg_eread, g->dbg_ne * 4);
     return PAG_OK;
 }
+
+/* test hook: the largest number of samples kept in one tile [1024 t, 1024 t + 1024) of k-mer start positions of a read strand */
+uint64_t pago_debug_max_tile_samples(const pago_graph *g) { return g->dbg_max_tile; }
 
 void pago_destroy(pago_graph *g) {
     if (!g) return;
@@ -377,12 +382,18 @@ static void add_position_and_edge(pago_graph *g, const char *seq, uint64_t len, 
     int64_t last = -1;
     int64_t prev_idx = -1;
     uint64_t prev_pos = 0;
+    uint64_t tile = UINT64_MAX, tile_kept = 0;
     for (uint64_t i = 0; i < n_codes; ++i) {
         if (off[i + 1] == off[i]) continue;
         int64_t idx = dense_index(g, codes[i]);
         if (idx < 0) continue;
         if (!(last < 0 || i - (uint64_t)last >= outer_sample)) continue;
         last = (int64_t)i;
+        if (i >> 10 != tile) {
+            tile = i >> 10;
+            tile_kept = 0;
+        }
+        if (++tile_kept > g->dbg_max_tile) g->dbg_max_tile = tile_kept;
         node_add_positions(&g->nodes[idx], lists + off[i], (size_t)(off[i + 1] - off[i]));
         *n_tuples += off[i + 1] - off[i];
         if (g->dbg) {

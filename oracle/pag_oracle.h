@@ -36,6 +36,8 @@ void pago_debug_enable(pago_graph *g, int on);
 int pago_debug_stream_sizes(const pago_graph *g, uint64_t *n_tuples, uint64_t *n_edges);
 int pago_debug_streams(const pago_graph *g, uint32_t *tkey, uint64_t *tval, uint32_t *ekey, uint64_t *eval);
 int pago_debug_stream_reads(const pago_graph *g, uint32_t *tread, uint32_t *eread);
+/* test hook: most samples kept in one 1024-position tile of a read strand since the last reset (K1's tile, k1_extract.hip) */
+uint64_t pago_debug_max_tile_samples(const pago_graph *g);
 
 /* function-level seams, exposed for known-answer tests */
 /* KmerHelper::kmer2Code (KmerHelper.cpp:7-25): writes len-k+1 codes, returns the count */

@@ -120,7 +120,7 @@ def walk_test_lib():
 class LoadedInput:
     """A pagraph input directory parsed by the product's host pipeline into the flat C-ABI input."""
 
-    def __init__(self, in_dir: str, threads: int = 1, eps: int = 10, cov: int = 2, block: int = 0):
+    def __init__(self, in_dir: str, threads: int = 1, eps: int = 10, cov: int = 2, block: int = 0, outer_sample=None):
         self.lib = test_lib()
         self.h = self.lib.pagh_load(in_dir.encode(), block, threads, eps, cov)
         if not self.h:
@@ -131,6 +131,15 @@ class LoadedInput:
         self.kmer_words = self.lib.pagh_kmer_words(self.h, C.byref(n), C.byref(k))
         self.n_kmer_words, self.k = n.value, k.value
         self.n_bases = self.lib.pagh_total_read_bases(self.h)
+        if outer_sample is not None:
+            self.set_outer_sample(outer_sample)
+
+    def set_outer_sample(self, outer: int):
+        """pagraph's outerSample (3, pagraph.cpp:113) replaced in both views: the host-prepared one (the oracle's, and
+        run_hip(prepare=False)) and the raw one pag_prepare turns into the device-resident input."""
+        from aligngraph2_amd.workload import PagBuildInput, PagRawInput
+        C.cast(self.view, C.POINTER(PagBuildInput)).contents.outer_sample = outer
+        C.cast(self.raw_view, C.POINTER(PagRawInput)).contents.outer_sample = outer
 
     def close(self):
         if self.h:
@@ -194,30 +203,68 @@ def _run(lib, prefix, g, inp: LoadedInput, streams: bool, prepared=None):
     return res
 
 
-def run_oracle(inp: LoadedInput, streams: bool = False):
+def run_oracle(inp: LoadedInput, streams: bool = False, solid_codes=None):
+    """solid_codes: a u64 array that replaces the input's solid-set file words (default: inp.kmer_words).  With streams,
+    res["max_tile_samples"] = the most samples kept in one 1024-position tile of a read strand (K1's tile)."""
     lib = oracle_lib()
-    g = lib.pago_create(inp.kmer_words, inp.n_kmer_words, inp.k)
+    if solid_codes is None:
+        g = lib.pago_create(inp.kmer_words, inp.n_kmer_words, inp.k)
+    else:
+        solid_codes = np.ascontiguousarray(solid_codes, dtype=np.uint64)
+        g = lib.pago_create(solid_codes.ctypes.data, len(solid_codes), inp.k)
     try:
         lib.pago_debug_enable(g, 1 if streams else 0)
-        return _run(lib, "pago", g, inp, streams)
+        res = _run(lib, "pago", g, inp, streams)
+        res["n_solid"] = lib.pago_solid_count(g)
+        if streams:
+            lib.pago_debug_max_tile_samples.argtypes = [C.c_void_p]
+            lib.pago_debug_max_tile_samples.restype = C.c_uint64
+            res["max_tile_samples"] = lib.pago_debug_max_tile_samples(g)
+        return res
     finally:
         lib.pago_destroy(g)
 
 
-def run_hip(inp: LoadedInput, streams: bool = False, device: int = 0, prepare: bool = True):
-    """The product path: pag_prepare (device) -> pag_process.  prepare=False feeds pag_process the host restatement's
-    arrays instead (the path the C ABI also accepts: host-resident pag_build_input)."""
+def hip_create(inp: LoadedInput, device: int = 0, solid_codes=None, solid_bitmap=None):
+    """pag_create from the input's solid-set file words, or from `solid_codes` (u64 array) instead, or
+    pag_create_from_bitmap from `solid_bitmap` (u32 array, 4^k bits, host memory; its set bits are counted here)."""
     lib = hip_lib()
-    if streams:
+    err = C.c_int()
+    if solid_bitmap is not None:
+        bits = np.ascontiguousarray(solid_bitmap, dtype=np.uint32)
+        n_solid = int(np.unpackbits(bits.view(np.uint8)).sum())
+        lib.pag_create_from_bitmap.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_int)]
+        lib.pag_create_from_bitmap.restype = C.c_void_p
+        g = lib.pag_create_from_bitmap(bits.ctypes.data, n_solid, inp.k, 0, device, C.byref(err))
+    elif solid_codes is not None:
+        codes = np.ascontiguousarray(solid_codes, dtype=np.uint64)
+        g = lib.pag_create(codes.ctypes.data, len(codes), inp.k, device, C.byref(err))
+    else:
+        g = lib.pag_create(inp.kmer_words, inp.n_kmer_words, inp.k, device, C.byref(err))
+    if not g:
+        raise RuntimeError(f"pag_create failed rc={err.value}: {lib.pag_last_error().decode()}")
+    return g
+
+
+def keep_streams(on: bool):
+    """PAG_DEBUG_KEEP_STREAMS: pag_process keeps copies of the emitted streams for pag_debug_streams"""
+    if on:
         os.environ["PAG_DEBUG_KEEP_STREAMS"] = "1"
     else:
         os.environ.pop("PAG_DEBUG_KEEP_STREAMS", None)
-    err = C.c_int()
-    g = lib.pag_create(inp.kmer_words, inp.n_kmer_words, inp.k, device, C.byref(err))
-    if not g:
-        raise RuntimeError(f"pag_create failed rc={err.value}: {lib.pag_last_error().decode()}")
+
+
+def run_hip(inp: LoadedInput, streams: bool = False, device: int = 0, prepare: bool = True, solid_codes=None, solid_bitmap=None):
+    """The product path: pag_prepare (device) -> pag_process.  prepare=False feeds pag_process the host restatement's
+    arrays instead (the path the C ABI also accepts: host-resident pag_build_input).  solid_codes / solid_bitmap: see
+    hip_create.  res["n_solid"] = pag_solid_count of the handle."""
+    lib = hip_lib()
+    keep_streams(streams)
+    g = hip_create(inp, device, solid_codes, solid_bitmap)
     try:
-        return _run(lib, "pag", g, inp, streams, _prepared_view(lib, g, inp) if prepare else None)
+        res = _run(lib, "pag", g, inp, streams, _prepared_view(lib, g, inp) if prepare else None)
+        res["n_solid"] = lib.pag_solid_count(g)
+        return res
     finally:
         lib.pag_destroy(g)
 

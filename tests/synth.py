@@ -168,6 +168,9 @@ class Spec:
     # stretch is taken out of the solid set, so that reads crossing it have edges whose step is the whole stretch
     homopolymer: tuple = ()
     desert: tuple = ()
+    # exact read lengths: read i (1-based) of the first len(read_lens) reads has read_lens[i - 1] bases (its fragment gets
+    # substitutions only, no indels); the other reads follow read_len / read_len_jitter.  Empty: no read is affected.
+    read_lens: tuple = ()
 
 
 def _aln_record(qname, rname, strand, score, qb, qe, qsize, rb, re_, rsize, qrow, rrow):
@@ -279,10 +282,13 @@ def generate(spec: Spec, out_dir: str) -> dict:
         L0 = spec.read_len
         if spec.read_len_jitter > 0:
             L0 = max(spec.k + 5, int(L0 * (1 + spec.read_len_jitter * (rng.random() * 2 - 1))))
+        exact = rid <= len(spec.read_lens)
+        if exact:
+            L0 = int(spec.read_lens[rid - 1])
         L0 = min(L0, TL - 1)
         s = int(rng.integers(0, TL - L0))
         src = target[s:s + L0]
-        frag, a_q, a_t = mutate(rng, src, spec.read_sub, spec.read_ins, spec.read_del)
+        frag, a_q, a_t = mutate(rng, src, spec.read_sub, 0.0 if exact else spec.read_ins, 0.0 if exact else spec.read_del)
         n = len(frag)
         read_rev = rng.random() < spec.rev_read_frac
         read = revcomp(frag) if read_rev else frag
