@@ -220,11 +220,10 @@ CNS_HD void init_backbone(Graph &g, const char *bb, uint32_t blen) {
     g.nf[g.exit_] = 1;
 }
 
-// addAln (:64-113)
-CNS_HD void add_aln(Graph &g, const char *q, const char *t, uint32_t len, uint32_t start, int weight) {
-    if (weight <= 0) return;
-    uint32_t bb_pos = start, prev = g.enter;
-    for (uint32_t i = 0; i < len && !g.err; ++i) {
+// addAln (:64-113) from column i on, with the backbone position and the previous vertex the columns before it left
+// (k_cns_wave.hip resumes here where its column-parallel form does not apply)
+CNS_HD void add_aln_from(Graph &g, const char *q, const char *t, uint32_t i, uint32_t len, uint32_t bb_pos, uint32_t prev, int weight) {
+    for (; i < len && !g.err; ++i) {
         const char qb = q[i], tb = t[i];
         const uint32_t cur = bb_pos;
         if (qb == tb) {  // match
@@ -253,6 +252,10 @@ CNS_HD void add_aln(Graph &g, const char *q, const char *t, uint32_t len, uint32
         }
     }
     if (!g.err) add_edge(g, prev, g.exit_, weight);
+}
+CNS_HD void add_aln(Graph &g, const char *q, const char *t, uint32_t len, uint32_t start, int weight) {
+    if (weight <= 0) return;
+    add_aln_from(g, q, t, 0, len, start, g.enter, weight);
 }
 
 // boost::clear_vertex for a bidirectional vecS graph + the slots of its edges handed back
@@ -476,8 +479,8 @@ CNS_HD void merge_nodes(Graph &g) {
     }
 }
 
-// bestPath (:383-467) + consensus (:293-333): the consensus string goes to out[0 .. *out_len)
-CNS_HD void consensus(Graph &g, int min_weight, char *out, uint32_t out_cap, uint32_t *out_len) {
+// bestPath (:383-467): every reached node's best out-edge (nbest) and score (nscore), from the exit vertex back
+CNS_HD void best_path(Graph &g) {
     // (edges(_g) only holds the edges that still exist; the flags of erased ones do not matter)
     for (uint32_t e = 0; e < g.n_edges_hi; ++e) g.ev[e] = 0;
     for (uint32_t v = 0; v < g.n_nodes; ++v) {
@@ -524,9 +527,10 @@ CNS_HD void consensus(Graph &g, int min_weight, char *out, uint32_t out_cap, uin
             if (not_visited == 0) q_push(g, q, in_node);
         }
     }
-    if (g.err) return;
-    // the path from the enter vertex along the best edges, its bases except those that look like the enter / exit vertex's;
-    // the longest stretch whose nodes all weigh at least min_weight (:293-333)
+}
+// consensus (:293-333) after best_path: the path from the enter vertex along the best edges, its bases except those that look
+// like the enter / exit vertex's; the longest stretch whose nodes all weigh at least min_weight goes to out[0 .. *out_len)
+CNS_HD void trim_path(Graph &g, int min_weight, char *out, uint32_t out_cap, uint32_t *out_len) {
     const uint8_t enter_base = g.nb[g.enter], exit_base = g.nb[g.exit_];
     uint32_t n_out = 0;
     int offs = 0, best_offs = 0, length = 0, idx = 0;
@@ -563,6 +567,12 @@ CNS_HD void consensus(Graph &g, int min_weight, char *out, uint32_t out_cap, uin
     // cns.substr(bestOffs, length), in place
     for (int i = 0; i < length; ++i) out[i] = out[best_offs + i];
     *out_len = (uint32_t)length;
+}
+// bestPath (:383-467) + consensus (:293-333): the consensus string goes to out[0 .. *out_len)
+CNS_HD void consensus(Graph &g, int min_weight, char *out, uint32_t out_cap, uint32_t *out_len) {
+    best_path(g);
+    if (g.err) return;
+    trim_path(g, min_weight, out, out_cap, out_len);
 }
 
 // one part, start to finish (pa_cns.cpp:98-124): backbone, its alignments in order, merge, consensus

@@ -5,15 +5,15 @@
 // bin/pa_cns can run (PA_CNS_BACKEND=flat).  What the device adds is many such streams side by side, each a chain of dependent
 // gathers the memory system overlaps across waves.  One LANE of a wave runs a part: with a part per lane (round 5) the 64
 // parts of a wave diverged at every branch and the wave executed them one after the other — 64 s for the 200 parts of a 1 Mb
-// backbone at 190x against 4 s on 16 host threads (profiles/r06_pa_cns_timing.json).
+// backbone at 190x against 4 s on 16 host threads (profiles/r06_pa_cns_timing.json).  k_cns_wave.hip puts the other lanes to
+// work (PA_CNS_BACKEND=wave).
 //
 // Memory: a part's node / edge / scratch regions come out of arrays allocated per batch; batches are cut so that a batch fits the
-// byte budget (free device memory x 0.8).
+// byte budget (free device memory x 0.8).  The batching is shared with k_cns_wave.hip (cns_device.hpp).
 #include <algorithm>
 #include <vector>
 
-#include "cns_graph.hpp"
-#include "pag_device.hpp"
+#include "cns_device.hpp"
 
 namespace pagdev {
 
@@ -30,7 +30,9 @@ __global__ __launch_bounds__(64) void cns_parts_kernel(pagcns::Arrays A, const p
 
 namespace {
 struct Dev {  // device allocations of one call, freed on every way out
+    const char *who;
     std::vector<void *> ptrs;
+    explicit Dev(const char *w) : who(w) {}
     ~Dev() {
         for (void *p : ptrs) (void)hipFree(p);
     }
@@ -39,7 +41,7 @@ struct Dev {  // device allocations of one call, freed on every way out
         void *p = nullptr;
         if (hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) {
             (void)hipGetLastError();
-            set_error("pag_cns_consensus: out of device memory (%zu bytes)", n * sizeof(T));
+            set_error("%s: out of device memory (%zu bytes)", who, n * sizeof(T));
             return PAG_ENOMEM;
         }
         ptrs.push_back(p);
@@ -47,26 +49,27 @@ struct Dev {  // device allocations of one call, freed on every way out
         return PAG_OK;
     }
 };
+
+void launch_lane(const pagcns::Arrays &A, const pagcns::Part *parts, uint32_t n, const char *backbone, const pagcns::Aln *alns, const char *qpool, const char *tpool,
+                 int min_weight, char *out, uint32_t *out_len, int32_t *part_err) {
+    cns_parts_kernel<<<dim3(n), dim3(64), 0, 0>>>(A, parts, n, backbone, alns, qpool, tpool, min_weight, out, out_len, part_err);
+}
 }  // namespace
 
-}  // namespace pagdev
-
-using namespace pagdev;
-
-extern "C" int pag_cns_consensus(int device, const char *backbone, uint64_t backbone_len, const pag_cns_part *parts, uint64_t n_parts, const pag_cns_aln *alns,
-                                 uint64_t n_alns, const char *qpool, const char *tpool, uint64_t pool_bytes, int32_t min_weight, char *out, uint64_t out_bytes,
-                                 uint64_t *out_off, uint32_t *out_len, int32_t *part_err) {
+int cns_consensus_batched(const char *who, CnsLaunchFn launch, int device, const char *backbone, uint64_t backbone_len, const pag_cns_part *parts, uint64_t n_parts,
+                          const pag_cns_aln *alns, uint64_t n_alns, const char *qpool, const char *tpool, uint64_t pool_bytes, int32_t min_weight, char *out,
+                          uint64_t out_bytes, uint64_t *out_off, uint32_t *out_len, int32_t *part_err) {
     static_assert(sizeof(pag_cns_aln) == sizeof(pagcns::Aln), "pag_cns_aln is pagcns::Aln");
     if (!backbone || (!parts && n_parts) || (!alns && n_alns) || !out || !out_off || !out_len || !part_err) return PAG_EINVAL;
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) {
         (void)hipGetLastError();
-        set_error("pag_cns_consensus: no gfx950 device %d (the consensus graphs are built on the device; PA_CNS_BACKEND=host is the host restatement)", device);
+        set_error("%s: no gfx950 device %d (the consensus graphs are built on the device; PA_CNS_BACKEND=host is the host restatement)", who, device);
         return PAG_ENODEV;
     }
     PAG_HIP_TRY(hipSetDevice(device));
     // inputs
-    Dev D;
+    Dev D(who);
     char *d_bb, *d_q, *d_t, *d_out;
     pagcns::Aln *d_alns;
     int rc;
@@ -87,7 +90,7 @@ extern "C" int pag_cns_consensus(int device, const char *backbone, uint64_t back
     }
     out_off[n_parts] = oo;
     if (oo > out_bytes) {
-        set_error("pag_cns_consensus: the output buffer holds %llu bytes, the parts may need %llu", (unsigned long long)out_bytes, (unsigned long long)oo);
+        set_error("%s: the output buffer holds %llu bytes, the parts may need %llu", who, (unsigned long long)out_bytes, (unsigned long long)oo);
         return PAG_EINVAL;
     }
     // batches of parts whose regions fit the budget
@@ -103,7 +106,7 @@ extern "C" int pag_cns_consensus(int device, const char *backbone, uint64_t back
             const uint64_t need = (nn + s.node_cap) * NODE_B + (ne + s.edge_cap) * EDGE_B + (na + s.aux_cap) * AUX_B;
             if (need > budget && p1 > p0) break;
             if (need > budget) {
-                set_error("pag_cns_consensus: part %llu alone needs %llu bytes of device memory, %llu are free", (unsigned long long)p1, (unsigned long long)need,
+                set_error("%s: part %llu alone needs %llu bytes of device memory, %llu are free", who, (unsigned long long)p1, (unsigned long long)need,
                           (unsigned long long)free_b);
                 return PAG_ENOMEM;
             }
@@ -126,7 +129,7 @@ extern "C" int pag_cns_consensus(int device, const char *backbone, uint64_t back
             na += s.aux_cap;
             ++p1;
         }
-        Dev B;
+        Dev B(who);
         pagcns::Arrays A{};
         pagcns::Part *d_parts;
         uint32_t *d_len;
@@ -140,7 +143,7 @@ extern "C" int pag_cns_consensus(int device, const char *backbone, uint64_t back
             return rc;
         PAG_HIP_TRY(hipMemcpy(d_parts, hp.data(), hp.size() * sizeof(pagcns::Part), hipMemcpyHostToDevice));
         const uint32_t n = (uint32_t)hp.size();
-        cns_parts_kernel<<<dim3(n), dim3(64), 0, 0>>>(A, d_parts, n, d_bb, d_alns, d_q, d_t, min_weight, d_out, d_len, d_err);
+        launch(A, d_parts, n, d_bb, d_alns, d_q, d_t, min_weight, d_out, d_len, d_err);
         PAG_HIP_TRY(hipGetLastError());
         PAG_HIP_TRY(hipDeviceSynchronize());
         PAG_HIP_TRY(hipMemcpy(out_len + p0, d_len, (size_t)n * 4, hipMemcpyDeviceToHost));
@@ -149,4 +152,13 @@ extern "C" int pag_cns_consensus(int device, const char *backbone, uint64_t back
     }
     if (oo) PAG_HIP_TRY(hipMemcpy(out, d_out, oo, hipMemcpyDeviceToHost));
     return PAG_OK;
+}
+
+}  // namespace pagdev
+
+extern "C" int pag_cns_consensus(int device, const char *backbone, uint64_t backbone_len, const pag_cns_part *parts, uint64_t n_parts, const pag_cns_aln *alns,
+                                 uint64_t n_alns, const char *qpool, const char *tpool, uint64_t pool_bytes, int32_t min_weight, char *out, uint64_t out_bytes,
+                                 uint64_t *out_off, uint32_t *out_len, int32_t *part_err) {
+    return pagdev::cns_consensus_batched("pag_cns_consensus", pagdev::launch_lane, device, backbone, backbone_len, parts, n_parts, alns, n_alns, qpool, tpool, pool_bytes,
+                                         min_weight, out, out_bytes, out_off, out_len, part_err);
 }

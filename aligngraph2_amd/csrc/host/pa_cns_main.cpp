@@ -5,11 +5,13 @@
 // (tools/cns/AlnGraphBoost.cpp: addAln / mergeNodes / bestPath / consensus) and the parts' consensus strings are written as
 // one FASTA record, 70 columns.
 //
-// Where the graphs are built (PA_CNS_BACKEND): `hip` (default) — on the device, one thread per part (pag_cns_consensus,
-// csrc/hip/k_cns.hip; the program fails without a gfx950 device, there is no silent fallback); `flat` — the device's code
-// (csrc/hip/cns_graph.hpp: flat arrays, linked edge lists) compiled for the host, a verification aid; `host` — the restatement
-// on std::vector / std::map below (AlnGraph), host code like the reference's, what the CPU tests pin on the goldens.  Reading,
-// slicing, gap normalisation, the per-part sort and the weights are host code in every case.
+// Where the graphs are built (PA_CNS_BACKEND): `hip` — on the device, one lane of a wavefront per part (pag_cns_consensus,
+// csrc/hip/k_cns.hip); `wave` — on the device, a wavefront per part whose lanes share the part's work (pag_cns_consensus_wave,
+// csrc/hip/k_cns_wave.hip); both fail without a gfx950 device, there is no silent fallback; `flat` — the device's code
+// (csrc/hip/cns_graph.hpp: flat arrays, linked edge lists) compiled for the host, on host threads; `host` — the restatement on
+// std::vector / std::map below (AlnGraph), host code like the reference's, what the CPU tests pin on the goldens.  `auto` (the
+// default) picks `hip` from kDevicePartsMin parts on and `flat` below.  Reading, slicing, gap normalisation, the per-part sort
+// and the weights are host code in every case.
 //
 // What has to be reproduced beyond the arithmetic, because it decides ties:
 //   * the graph is boost::adjacency_list<vecS, vecS, bidirectionalS>: out- and in-edge lists are vectors in insertion order,
@@ -24,6 +26,7 @@
 #include <algorithm>
 #include <atomic>
 #include <cfloat>
+#include <chrono>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -599,7 +602,7 @@ struct HipLibrary {
                                 std::uint64_t, std::int32_t, char *, std::uint64_t, std::uint64_t *, std::uint32_t *, std::int32_t *);
     using ErrorFn = const char *(*)();
     void *handle = nullptr;
-    ConsensusFn consensus = nullptr;
+    ConsensusFn consensus = nullptr, consensus_wave = nullptr;
     ErrorFn last_error = nullptr;
     explicit HipLibrary(const char *argv0) {
         std::string dir = argv0 ? argv0 : "";
@@ -610,8 +613,9 @@ struct HipLibrary {
         if (!handle) handle = dlopen("libpagraph_hip.so", RTLD_NOW | RTLD_LOCAL);
         if (!handle) throw std::runtime_error(std::string("the device backend needs libpagraph_hip.so: ") + dlerror());
         consensus = reinterpret_cast<ConsensusFn>(dlsym(handle, "pag_cns_consensus"));
+        consensus_wave = reinterpret_cast<ConsensusFn>(dlsym(handle, "pag_cns_consensus_wave"));
         last_error = reinterpret_cast<ErrorFn>(dlsym(handle, "pag_last_error"));
-        if (!consensus || !last_error) throw std::runtime_error("libpagraph_hip.so does not export pag_cns_consensus");
+        if (!consensus || !consensus_wave || !last_error) throw std::runtime_error("libpagraph_hip.so does not export pag_cns_consensus / pag_cns_consensus_wave");
     }
     HipLibrary(const HipLibrary &) = delete;
     HipLibrary &operator=(const HipLibrary &) = delete;
@@ -656,8 +660,9 @@ int main(int argc, char **argv) {
         std::atomic<std::size_t> consensusLen(0), next(0);
         std::atomic<bool> failed(false);
         std::string failure;
-        // Where the per-part graphs are built.  hip: one device thread per part (csrc/hip/k_cns.hip) — the library is loaded when, and
-        // only when, this backend runs: the program starts on a machine without the ROCm runtime; flat: the device's code
+        // Where the per-part graphs are built.  hip: one device thread per part (csrc/hip/k_cns.hip); wave: a wavefront per part with
+        // its lanes on the columns of an alignment and the levels of bestPath (csrc/hip/k_cns_wave.hip) — the library is loaded when,
+        // and only when, a device backend runs: the program starts on a machine without the ROCm runtime; flat: the device's code
         // (csrc/hip/cns_graph.hpp) on host threads; host: the std::vector / std::map restatement.  Default: by the number of parts —
         // a part is a serial chain of dependent accesses, the device wins by running thousands side by side, host threads win on
         // the few hundred parts of one contig of the pipeline (AlignGraph2.py:503 calls pa_cns once per new contig;
@@ -665,8 +670,16 @@ int main(int argc, char **argv) {
         const char *backendEnv = std::getenv("PA_CNS_BACKEND");
         std::string backend = backendEnv ? backendEnv : "auto";
         if (backend == "auto") backend = partNum >= kDevicePartsMin ? "hip" : "flat";
-        if (backend != "hip" && backend != "flat" && backend != "host") throw std::runtime_error("PA_CNS_BACKEND must be hip, flat, host or auto");
+        if (backend != "hip" && backend != "wave" && backend != "flat" && backend != "host")
+            throw std::runtime_error("PA_CNS_BACKEND must be hip, wave, flat, host or auto");
         const bool onHost = backend == "host";
+        // PA_CNS_STAGE_TIMES=1: the graph stage's seconds on stderr (a host clock around the backend call, which ends in a device
+        // synchronise; `host` builds its graphs inside the per-part sort, so its figure holds the sort too) and, for `flat`, the
+        // thread-seconds of its three phases
+        const bool stageTimes = pagh::envInt("PA_CNS_STAGE_TIMES", 0) != 0;
+        using Clock = std::chrono::steady_clock;
+        const auto seconds = [](Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
+        const auto tSort = Clock::now();
         std::vector<std::vector<std::size_t>> partWeights(partNum);
         auto work = [&]() {
             for (std::size_t i; (i = next.fetch_add(1)) < partNum;) {
@@ -708,6 +721,7 @@ int main(int argc, char **argv) {
             for (auto &t : pool) t.join();
         }
         if (failed) throw std::runtime_error(failure);
+        if (stageTimes && onHost) std::cerr << "pa_cns: graph stage (host, with the per-part sort) " << seconds(tSort, Clock::now()) << " s" << std::endl;
         if (!onHost) {
             // the parts as flat arrays: every alignment's two rows in two pools, the regions of every part's graph sized from its
             // columns (include/pagraph_hip.h, pag_cns_consensus)
@@ -753,12 +767,22 @@ int main(int argc, char **argv) {
             std::vector<std::uint64_t> outOff(partNum + 1, 0);
             std::vector<std::uint32_t> outLen(partNum, 0);
             std::vector<std::int32_t> partErr(partNum, 0);
-            if (backend == "hip") {
+            std::atomic<long long> phaseNs[3] = {{0}, {0}, {0}};  // flat under PA_CNS_STAGE_TIMES: add_aln, merge_nodes, best_path + trim
+            auto tGraph = Clock::now();
+            if (backend == "hip" || backend == "wave") {
                 const int device = static_cast<int>(pagh::envInt("PAGRAPH_DEVICE", 0));
                 const HipLibrary hip(argv[0]);  // (throws when the library or a gfx950 device is missing: there is no silent fallback)
-                const int rc = hip.consensus(device, backbone.data(), backbone.size(), parts.data(), partNum, flat.data(), flat.size(), qpool.data(), tpool.data(),
-                                             qpool.size(), 0, outBuf.data(), outBytes, outOff.data(), outLen.data(), partErr.data());
-                if (rc != 0) throw std::runtime_error(std::string("pag_cns_consensus failed (") + std::to_string(rc) + "): " + hip.last_error());
+                const bool wave = backend == "wave";
+                if (stageTimes) {  // (the HIP runtime's start and the code object's load stay out of the stage's clock)
+                    const auto available = reinterpret_cast<int (*)()>(dlsym(hip.handle, "pag_device_available"));
+                    if (available) (void)available();
+                    tGraph = Clock::now();
+                }
+                const int rc = (wave ? hip.consensus_wave : hip.consensus)(device, backbone.data(), backbone.size(), parts.data(), partNum, flat.data(), flat.size(),
+                                                                           qpool.data(), tpool.data(), qpool.size(), 0, outBuf.data(), outBytes, outOff.data(),
+                                                                           outLen.data(), partErr.data());
+                if (rc != 0)
+                    throw std::runtime_error(std::string(wave ? "pag_cns_consensus_wave" : "pag_cns_consensus") + " failed (" + std::to_string(rc) + "): " + hip.last_error());
             } else {  // the device's code on host threads
                 std::uint64_t oo = 0;
                 for (std::size_t i = 0; i < partNum; ++i) {
@@ -791,7 +815,28 @@ int main(int argc, char **argv) {
                         P.out_cap = S.out_cap;
                         static_assert(sizeof(pag_cns_aln) == sizeof(pagcns::Aln), "pag_cns_aln is pagcns::Aln");
                         std::uint32_t len = 0;
-                        partErr[i] = pagcns::run_part(A, P, backbone.data(), reinterpret_cast<const pagcns::Aln *>(flat.data()), qpool.data(), tpool.data(), 0, outBuf.data(), &len);
+                        const auto *fa = reinterpret_cast<const pagcns::Aln *>(flat.data());
+                        if (!stageTimes) {
+                            partErr[i] = pagcns::run_part(A, P, backbone.data(), fa, qpool.data(), tpool.data(), 0, outBuf.data(), &len);
+                        } else {  // run_part's steps with a clock between them
+                            pagcns::Graph g;
+                            pagcns::bind(g, A, P);
+                            const auto t0 = Clock::now();
+                            pagcns::init_backbone(g, backbone.data() + P.bb_off, P.bb_len);
+                            for (std::uint32_t a = 0; a < P.n_aln && !g.err; ++a) {
+                                const pagcns::Aln &al = fa[P.aln_first + a];
+                                pagcns::add_aln(g, qpool.data() + al.str_off, tpool.data() + al.str_off, al.len, al.start, al.weight);
+                            }
+                            const auto t1 = Clock::now();
+                            if (!g.err) pagcns::merge_nodes(g);
+                            const auto t2 = Clock::now();
+                            if (!g.err) pagcns::consensus(g, 0, outBuf.data() + P.out_off, P.out_cap, &len);
+                            const auto t3 = Clock::now();
+                            phaseNs[0] += std::chrono::duration_cast<std::chrono::nanoseconds>(t1 - t0).count();
+                            phaseNs[1] += std::chrono::duration_cast<std::chrono::nanoseconds>(t2 - t1).count();
+                            phaseNs[2] += std::chrono::duration_cast<std::chrono::nanoseconds>(t3 - t2).count();
+                            partErr[i] = g.err;
+                        }
                         outLen[i] = partErr[i] ? 0 : len;
                     }
                 };
@@ -799,6 +844,12 @@ int main(int argc, char **argv) {
                 for (unsigned t = 1; t < nThreads; ++t) pool.emplace_back(flatWork);
                 flatWork();
                 for (auto &t : pool) t.join();
+            }
+            if (stageTimes) {
+                std::cerr << "pa_cns: graph stage (" << backend << ") " << seconds(tGraph, Clock::now()) << " s" << std::endl;
+                if (backend == "flat")
+                    std::cerr << "pa_cns: flat phases (thread-seconds) add_aln " << phaseNs[0] * 1e-9 << " merge_nodes " << phaseNs[1] * 1e-9 << " best_path+trim "
+                              << phaseNs[2] * 1e-9 << std::endl;
             }
             for (std::size_t i = 0; i < partNum; ++i) {
                 if (partErr[i] == pagcns::CNS_E_OVERRUN) throw std::runtime_error("pa_cns: an alignment runs past the end of its part");

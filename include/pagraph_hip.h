@@ -475,6 +475,13 @@ typedef struct pag_cns_part {
 int pag_cns_consensus(int device, const char *backbone, uint64_t backbone_len, const pag_cns_part *parts, uint64_t n_parts, const pag_cns_aln *alns,
                       uint64_t n_alns, const char *qpool, const char *tpool, uint64_t pool_bytes, int32_t min_weight, char *out, uint64_t out_bytes,
                       uint64_t *out_off, uint32_t *out_len, int32_t *part_err);
+/* The same call with the same inputs, results and error codes, and the same bytes: a wavefront per part whose lanes share the
+ * part's work — the columns of an alignment 64 at a time in addAln, the nodes of a level in bestPath (mergeNodes runs on one
+ * lane).  Regions are sized as for pag_cns_consensus. */
+int pag_cns_consensus_wave(int device, const char *backbone, uint64_t backbone_len, const pag_cns_part *parts, uint64_t n_parts,
+                           const pag_cns_aln *alns, uint64_t n_alns, const char *qpool, const char *tpool, uint64_t pool_bytes,
+                           int32_t min_weight, char *out, uint64_t out_bytes, uint64_t *out_off, uint32_t *out_len,
+                           int32_t *part_err);
 
 typedef struct pag_kmer_count_result {
     uint64_t min_abundance;
