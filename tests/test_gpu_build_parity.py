@@ -48,7 +48,8 @@ def test_build_matches_oracle(name, workdir):
 @pytest.mark.parametrize("segments,seed", [(2000, 1), (20000, 2), (300000, 3)])
 def test_segment_kernels_match_sequential_restatement(segments, seed, wide):
     """K3/K4 alone (both widths of the short path, segments on both sides of every limit of the on-chip long paths, tile halos) against
-    a sequential greedy scan / sort-unique."""
+    a sequential greedy scan / sort-unique, on random segment lengths at eps 10.  (Segments placed ON every limit, counts that wrap, the
+    other eps: test_gpu_segment_shapes.py.)"""
     import subprocess
     exe = os.path.join(pagctl.ROOT, "tests", "harness", "bin", "seg_kernels_test")
     assert os.path.exists(exe), "run `make harness`"
@@ -60,8 +61,9 @@ def test_segment_kernels_match_sequential_restatement(segments, seed, wide):
 @pytest.mark.parametrize("n,bits", [(1, 5), (64, 6), (5000, 13), (5120, 14), (5121, 14), (7000, 32), (100000, 21), (1000003, 25),
                                     (10000000, 28)])
 def test_radix_sort_is_a_stable_sort(n, bits):
-    """K2 alone (tests/harness/sort_bench.hip): random keys of `bits` bits, payload = input index; the result must equal
-    std::stable_sort's — full and partial tiles, one block and many, every digit width the pass splitter produces."""
+    """K2 alone (tests/harness/sort_bench.hip): random keys of `bits` bits, payload = a hash of the input index in the high half and the
+    index in the low half; the result must equal std::stable_sort's — full and partial tiles, one block and many, every digit width the
+    pass splitter produces.  (Skewed keys, unaligned views, tile counts around the persistent grid: test_gpu_segment_shapes.py.)"""
     exe = os.path.join(pagctl.ROOT, "tests", "harness", "bin", "sort_bench")
     if not os.path.exists(exe):
         pytest.skip("tests/harness/bin/sort_bench not built")
