@@ -73,6 +73,11 @@ def load_hip():
         lib.pag_travel_view_sizes.restype = C.c_int
         lib.pag_travel_path_oriented.argtypes = [vp, C.c_uint64, C.c_int, u64p]
         lib.pag_travel_path_oriented.restype = vp
+        # the path dumps' text rendered on the device: records -> text, and what pag_travel rendered for a delivered contig
+        lib.pag_render_dump_lines.argtypes = [vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, u64p, C.c_int]
+        lib.pag_render_dump_lines.restype = C.c_int
+        lib.pag_travel_dump_text.argtypes = [vp, C.c_uint64, C.c_int, u64p]
+        lib.pag_travel_dump_text.restype = vp
         _hip["lib"] = lib
     return _hip["lib"]
 

@@ -63,6 +63,15 @@ const pag_path_node *pag_travel_path_oriented(const pag_graph *g, uint64_t ctg_i
     return g->path_store + g->path_off[slot];
 }
 
+// ... and its dump text when pag_travel was asked for it (PAG_TRAVEL_RENDER_DUMPS) and could render it
+const char *pag_travel_dump_text(const pag_graph *g, uint64_t ctg_index, int forward, uint64_t *bytes) {
+    const uint64_t slot = 2 * ctg_index + (forward ? 0 : 1);
+    if (bytes) *bytes = 0;
+    if (!g || slot >= g->path_valid.size() || !g->path_valid[slot] || slot >= g->text_ptr.size() || !g->text_ptr[slot]) return nullptr;
+    if (bytes) *bytes = g->text_len[slot];
+    return g->text_ptr[slot];
+}
+
 const pag_path_node *pag_travel_path(const pag_graph *g, uint64_t ctg_index, uint64_t *len) {
     if (g && 2 * ctg_index + 1 < g->path_valid.size() && !g->path_valid[2 * ctg_index]) return pag_travel_path_oriented(g, ctg_index, 0, len);
     return pag_travel_path_oriented(g, ctg_index, 1, len);

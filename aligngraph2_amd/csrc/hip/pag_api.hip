@@ -86,6 +86,8 @@ void free_graph_results(pag_graph *g) {  // the memory stays in the pool
     g->path_len.clear();
     g->path_valid.clear();
     g->path_ptr.clear();
+    g->text_ptr.clear();
+    g->text_len.clear();
 }
 
 __global__ void chunk_counts(const pag_aln *__restrict__ aln, uint64_t n, uint32_t *__restrict__ out) {
@@ -257,6 +259,8 @@ void pag_destroy(pag_graph *g) {
     g->fetch_chunks.clear();
     g->fetch_chunk_bytes.clear();
     if (g->walk_arena) hipFree(g->walk_arena);
+    if (g->dump_tables) hipFree(g->dump_tables);
+    if (g->dump_scratch) hipFree(g->dump_scratch);
     if (g->wq_next) hipFree(g->wq_next);
     for (hipStream_t ws : g->walk_streams) hipStreamDestroy(ws);
     if (g->solid_bits) hipFree(g->solid_bits);
@@ -673,7 +677,10 @@ extern "C" int pag_reserve_walk_arena(pag_graph *g, uint64_t contig_bases) {
         const size_t FETCH_CHUNK = 64u << 20;
         size_t have = 0;
         for (size_t b : g->fetch_chunk_bytes) have += b;
-        const size_t want_pinned = std::min<size_t>((size_t)contig_bases * 14, (size_t)4 << 30);
+        // (PAGRAPH_DEVICE_DUMPS=1, the switch of the callers that will ask pag_travel for the dump text: its buffers come out of the
+        // same chunks, ~0.24 path vertices per contig base at up to ~90 bytes of a line's bound)
+        const size_t per_base = 14 + (env_int("PAGRAPH_DEVICE_DUMPS", 0) == 1 ? 22 : 0);
+        const size_t want_pinned = std::min<size_t>((size_t)contig_bases * per_base, (size_t)4 << 30);
         while (have < want_pinned) {
             void *q = nullptr;
             if (hipHostMalloc(&q, FETCH_CHUNK, hipHostMallocDefault) != hipSuccess) {

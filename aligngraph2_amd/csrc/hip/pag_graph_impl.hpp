@@ -63,6 +63,12 @@ struct pag_graph {
     hipStream_t deliver_stream = nullptr;  // copies of finished contigs' paths while the walks run (pag_travel)
     std::vector<const pag_path_node *> path_ptr;  // non-null: the orientation's path, delivered while the walks ran (pinned fetch memory)
     std::vector<uint8_t> path_valid;  // that orientation was traversed by the last pag_travel
+    // the dump text of the delivered paths (PAG_TRAVEL_RENDER_DUMPS; pinned fetch memory like path_ptr) and the device memory
+    // the renderings use: the PositionMapper tables, the scratch of the epilogue's renderings
+    std::vector<const char *> text_ptr;
+    std::vector<uint64_t> text_len;
+    void *dump_tables = nullptr, *dump_scratch = nullptr;
+    size_t dump_tables_cap = 0, dump_scratch_cap = 0;
     // device arena of the walker's job buffers (bump pointer, reset by every pag_travel)
     void *walk_arena = nullptr;
     size_t walk_arena_cap = 0, walk_arena_used = 0;

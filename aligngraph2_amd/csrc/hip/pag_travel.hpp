@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "pagraph_hip.h"
 
 namespace pagdev {
@@ -248,5 +250,25 @@ struct TravConcatPart {
 };
 void trav_launch_concat_parts(const TravConcatPart *parts, uint32_t n_parts, uint32_t *out_v, uint32_t *out_s, uint32_t first_step,
                               hipStream_t s);
+
+// ---- the text of a path dump (k5_dump.hip) ---------------------------------------------------------------------------
+// PositionMapper's tables of the contigs and of the references as the device reads them (u32: dump_tables_build refuses
+// coordinate spaces beyond 32 bits and more than DUMP_MAX_SEQS sequences, which also bounds a line's length); the starts of
+// both go to LDS when they have DUMP_LDS_STARTS entries or fewer.
+constexpr uint32_t DUMP_LDS_STARTS = 5632u, DUMP_MAX_SEQS = 99999999u;
+struct DumpTables {
+    const uint32_t *cstart, *csize, *rstart, *rsize;  // [nc + 1] [nc] [nr + 1] [nr]
+    uint32_t nc, nr, in_lds;
+};
+// host arrays -> one blob in the layout dump_tables_at() reads (after it was copied to the device); false: out of bounds
+bool dump_tables_build(const uint32_t *ctg_len, uint64_t n_ctgs, const uint32_t *ref_len, uint64_t n_refs, std::vector<uint32_t> &blob);
+DumpTables dump_tables_at(const uint32_t *dev, uint64_t n_ctgs, uint64_t n_refs);
+uint32_t dump_line_bound(uint32_t k, const std::vector<uint32_t> &blob, uint64_t n_ctgs, uint64_t n_refs);
+size_t dump_scratch_bytes(uint64_t n);  // device scratch of one rendering of n lines (256-byte multiple)
+// the lines of a path (new ids + steps, as trav_launch_gather_path takes them) into `out` (device or pinned host memory, 16-byte
+// aligned buffer start not required); *total_host (pinned, may be null) receives the text's size — nothing is written when it
+// exceeds cap.  max_blocks as for trav_launch_gather_path.
+int trav_launch_dump_path(TravGraph G, const uint32_t *seq_v, const uint32_t *seq_s, uint64_t len, uint32_t k, const DumpTables &T, void *scratch,
+                          char *out, uint64_t cap, uint64_t *total_host, hipStream_t s, unsigned max_blocks);
 
 }  // namespace pagdev

@@ -28,6 +28,7 @@ struct WalkConfig {
     bool check_aggs = false;          // PAG_DEBUG_CHECK_AGGS
     int debug_seqcap = 0;             // PAG_DEBUG_SEQCAP (> 0: tiny initial walk buffers)
     int debug_ring = 0;               // PAG_DEBUG_RING (> 0: job rings of that many entries)
+    bool debug_deliver_late = false;  // PAG_DEBUG_DELIVER_LATE: no contig is delivered (or put together on the device) while the walks run: all of them are left to the epilogue
     uint64_t debug_emit_cap = 0;      // PAG_DEBUG_EMIT_CAP (> 0: the first emission stream of the successor records has that many slots: the grow-and-repeat path)
     // ---- pieces
     bool pieces = true;               // PAG_WALK_PIECES
@@ -66,6 +67,7 @@ struct WalkConfig {
         if (u64("PAG_DEBUG_SEQCAP", &x)) c.debug_seqcap = (int)std::max<uint64_t>(16, std::min<uint64_t>(x, 1u << 30));
         if (u64("PAG_DEBUG_RING", &x)) c.debug_ring = (int)std::max<uint64_t>(4, std::min<uint64_t>(x, 1u << 30));
         u64("PAG_DEBUG_EMIT_CAP", &c.debug_emit_cap);
+        c.debug_deliver_late = given("PAG_DEBUG_DELIVER_LATE");
         c.pieces = !off("PAG_WALK_PIECES");
         c.leap_pieces = !off("PAG_LEAP_PIECES");
         c.force_exact = given("PAG_WALK_EXACT");

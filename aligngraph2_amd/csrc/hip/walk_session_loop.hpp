@@ -435,7 +435,7 @@ struct WalkSession : WalkRounds {
                 }
                 if (!base.empty()) dist = (int32_t)(head_ctg - base.back().ctg);
                 const size_t at0 = base.size();
-                if (P.leap && !RS[i].slot_bufs && g->walk_arena) {
+                if (P.leap && !RS[i].slot_bufs && g->walk_arena && !cfg.debug_deliver_late) {
                     // the contig is finished by this walk (splice below): nothing of it is needed on the host
                     bool on_dev = true;
                     for (const Chain::Part &pt : ch.parts) on_dev = on_dev && pt.dv && pt.ds;
@@ -821,9 +821,11 @@ struct WalkSession : WalkRounds {
             uint32_t *hp = (uint32_t *)pinned(tot * 8 + 256);
             if (!hp) return fail(PAG_ENOMEM);
             uint64_t at = 0;
+            size_t scratch_bytes = 0;
             for (auto &cs : st) {
                 if (cs.delivered) continue;
                 const size_t slot2 = 2 * (size_t)cs.ci + (cs.forward ? 0 : 1);
+                if (render && !cs.travel.empty()) scratch_bytes += dump_scratch_bytes(cs.travel.size());
                 g->path_off[slot2] = at;
                 g->path_len[slot2] = cs.travel.size();
                 g->path_valid[slot2] = 1;
@@ -840,8 +842,35 @@ struct WalkSession : WalkRounds {
                 trav_launch_gather_path(G, b_fin.as<uint32_t>(), b_fin.as<uint32_t>() + tot, tot, b_gather.as<pag_path_node>(), s);
                 PAG_HIP_TRY(hipMemcpyAsync(g->path_store, b_gather.p, tot * sizeof(pag_path_node), hipMemcpyDeviceToHost, s));
             }
+            if (render && scratch_bytes) {  // the dump text of those sequences: one rendering per contig, at full width (no walk is live)
+                if (g->dump_scratch_cap < scratch_bytes) {
+                    if (g->dump_scratch) PAG_HIP_TRY(hipFree(g->dump_scratch));
+                    g->dump_scratch = nullptr;
+                    g->dump_scratch_cap = 0;
+                    PAG_HIP_TRY(hipMalloc(&g->dump_scratch, scratch_bytes + scratch_bytes / 4));
+                    g->dump_scratch_cap = scratch_bytes + scratch_bytes / 4;
+                }
+                size_t sat = 0;
+                for (auto &cs : st) {
+                    if (cs.delivered || cs.travel.empty()) continue;
+                    const size_t slot2 = 2 * (size_t)cs.ci + (cs.forward ? 0 : 1);
+                    const uint32_t *ids = b_fin.as<uint32_t>() + g->path_off[slot2];
+                    if ((rc = render_path(slot2, ids, ids + tot, cs.travel.size(), (char *)g->dump_scratch + sat, s, 0u))) return fail(rc);
+                    ++n_epilogue_texts;
+                    sat += dump_scratch_bytes(cs.travel.size());
+                }
+            }
             PAG_HIP_TRY(hipStreamSynchronize(s));
             if (g->deliver_stream) PAG_HIP_TRY(hipStreamSynchronize(g->deliver_stream));  // (the deliveries made during the walks)
+            resolve_texts();
+            if (timing && render) {
+                size_t n_text = 0, n_none = 0;
+                for (auto &cs : st) {
+                    const size_t slot2 = 2 * (size_t)cs.ci + (cs.forward ? 0 : 1);
+                    if (g->path_len[slot2]) (g->text_ptr[slot2] ? n_text : n_none) += 1;
+                }
+                std::fprintf(stderr, "[timing] dump text: %zu contigs rendered (%zu of them in the epilogue), %zu left to the host\n", n_text, n_epilogue_texts, n_none);
+            }
         }
         lap("epilogue");
         if (timing) {

@@ -320,6 +320,9 @@ struct WalkRounds : WalkJobs {
         hipStreamSynchronize(s);
         std::fill(g->path_valid.begin(), g->path_valid.end(), (uint8_t)0);
         std::fill(g->path_ptr.begin(), g->path_ptr.end(), nullptr);
+        std::fill(g->text_ptr.begin(), g->text_ptr.end(), nullptr);
+        std::fill(g->text_len.begin(), g->text_len.end(), (uint64_t)0);
+        text_pending.clear();
         return rc2;
     }
 
@@ -355,6 +358,63 @@ struct WalkRounds : WalkJobs {
     // (a delivery issued while walk jobs are live runs on 24 blocks: its thousands of waves, each with stores to host memory in
     // flight, slowed every walker wave beside them — 2.5 -> 3.2-5 us per classification in the last 40 ms of a block, round 5)
     static constexpr unsigned DELIVER_BLOCKS = 24;
+    // PAG_TRAVEL_RENDER_DUMPS: the dump text of every delivered path (k5_dump.hip) — from the same ids, on the same stream and
+    // under the same block cap as its gather, stored straight into pinned memory like the records.  The buffer is sized by a
+    // bound (dump_line_bound); the text's size arrives in front of it and is read when the stream has been waited for
+    // (resolve_texts): a text that did not fit was not written and the caller formats the records itself.
+    bool render = false;
+    DumpTables dump_tab{};
+    uint32_t dump_bound = 0;
+    std::vector<uint32_t> dump_blob;
+    struct TextPending {
+        size_t slot2;
+        char *buf;  // [u64 size, padding to 256][text]
+        uint64_t cap;
+    };
+    std::vector<TextPending> text_pending;
+    size_t n_epilogue_texts = 0;
+    int setup_render() {
+        render = false;
+        if (!(prm->reserved & PAG_TRAVEL_RENDER_DUMPS) || !dump_tables_build(ctgs->len, ctgs->n_seqs, ref_len, n_refs, dump_blob)) return PAG_OK;
+        const size_t bytes = dump_blob.size() * 4 + 16;
+        if (g->dump_tables_cap < bytes) {
+            if (g->dump_tables) PAG_HIP_TRY(hipFree(g->dump_tables));
+            g->dump_tables = nullptr;
+            g->dump_tables_cap = 0;
+            PAG_HIP_TRY(hipMalloc(&g->dump_tables, bytes + bytes / 4));
+            g->dump_tables_cap = bytes + bytes / 4;
+        }
+        if (!dump_blob.empty()) PAG_HIP_TRY(hipMemcpyAsync(g->dump_tables, dump_blob.data(), dump_blob.size() * 4, hipMemcpyHostToDevice, s));
+        dump_tab = dump_tables_at((const uint32_t *)g->dump_tables, ctgs->n_seqs, n_refs);
+        dump_bound = dump_line_bound(k, dump_blob, ctgs->n_seqs, n_refs);
+        render = true;
+        return PAG_OK;
+    }
+    int render_path(size_t slot2, const uint32_t *d_v, const uint32_t *d_s, size_t m, void *scratch, hipStream_t st, unsigned max_blocks) {
+        const uint64_t cap = (uint64_t)m * dump_bound;
+        char *buf = (char *)fetch_alloc(256 + cap);
+        if (!buf) return PAG_OK;  // (no pinned memory for the text, which is an extra: the caller formats that contig's records itself)
+        *(uint64_t *)buf = ~0ull;
+        int rc2 = trav_launch_dump_path(G, d_v, d_s, m, k, dump_tab, scratch, buf + 256, cap, (uint64_t *)buf, st, max_blocks);
+        if (rc2 == PAG_OK) text_pending.push_back(TextPending{slot2, buf, cap});
+        return rc2;
+    }
+    void *arena_scratch(size_t m) {  // (nullptr: no room — that contig's text is left to the caller)
+        const size_t need = dump_scratch_bytes(m);
+        if (!g->walk_arena || g->walk_arena_used + need > g->walk_arena_cap) return nullptr;
+        void *q = (char *)g->walk_arena + g->walk_arena_used;
+        g->walk_arena_used += need;
+        return q;
+    }
+    void resolve_texts() {  // (after the streams of all renderings have been waited for)
+        for (const TextPending &t : text_pending) {
+            const uint64_t total = *(const volatile uint64_t *)t.buf;
+            if (total > t.cap) continue;
+            g->text_ptr[t.slot2] = t.buf + 256;
+            g->text_len[t.slot2] = total;
+        }
+        text_pending.clear();
+    }
     int deliver_contig(uint32_t i) {
         CtgState &cs = st[i];
         if (cs.delivered || !cs.done) return PAG_OK;
@@ -381,10 +441,16 @@ struct WalkRounds : WalkJobs {
             }
             trav_launch_gather_path(G, T.d_ids, T.d_ids + T.cap, m, dst, g->deliver_stream, n_live ? DELIVER_BLOCKS : 0u);
             g->path_ptr[slot2] = dst;
+            if (render) {
+                void *scratch = arena_scratch(m);
+                int rc2;
+                if (scratch && (rc2 = render_path(slot2, T.d_ids, T.d_ids + T.cap, m, scratch, g->deliver_stream, n_live ? DELIVER_BLOCKS : 0u))) return rc2;
+            }
             return PAG_OK;
         }
+        if (cfg.debug_deliver_late) return PAG_OK;
         const size_t n = cs.travel.size();
-        const size_t need = ((n * 8 + 255) & ~(size_t)255) + 512;
+        const size_t need = ((n * 8 + 255) & ~(size_t)255) + 512 + (render ? dump_scratch_bytes(n) : 0);
         if (!g->walk_arena || g->walk_arena_used + need > g->walk_arena_cap) return PAG_OK;
         filter_travel(cs);
         const size_t m = cs.travel.size();
@@ -410,6 +476,11 @@ struct WalkRounds : WalkJobs {
         PAG_HIP_TRY(hipMemcpyAsync(d_ids, hp, m * 8, hipMemcpyHostToDevice, g->deliver_stream));
         trav_launch_gather_path(G, d_ids, d_ids + m, m, dst, g->deliver_stream, n_live ? DELIVER_BLOCKS : 0u);
         g->path_ptr[slot2] = dst;
+        if (render) {
+            void *scratch = arena_scratch(m);
+            int rc2;
+            if (scratch && (rc2 = render_path(slot2, d_ids, d_ids + m, m, scratch, g->deliver_stream, n_live ? DELIVER_BLOCKS : 0u))) return rc2;
+        }
         return PAG_OK;
     }
 
@@ -465,6 +536,8 @@ struct WalkRounds : WalkJobs {
         g->path_len.assign(2 * (size_t)n_ctgs, 0);
         g->path_valid.assign(2 * (size_t)n_ctgs, 0);
         g->path_ptr.assign(2 * (size_t)n_ctgs, nullptr);
+        g->text_ptr.assign(2 * (size_t)n_ctgs, nullptr);
+        g->text_len.assign(2 * (size_t)n_ctgs, 0);
         // one entry per (contig, orientation): a contig selected with both orientations is two independent traversals
         // (PAssembly.cpp:28-36 walks every (name, forward) pair of its set)
         for (uint32_t c2 = 0; c2 < 2 * n_ctgs; ++c2) {
@@ -499,6 +572,7 @@ struct WalkRounds : WalkJobs {
         PAG_HIP_TRY(hipMemcpyAsync(b_packed.p, ctgs->packed, ctgs->packed_bytes, hipMemcpyHostToDevice, s));
         PAG_HIP_TRY(hipMemcpyAsync(b_starts.p, mapper.starts.data(), mapper.starts.size() * 8, hipMemcpyHostToDevice, s));
         PAG_HIP_TRY(hipMemcpyAsync(b_sizes.p, mapper.sizes.data(), mapper.sizes.size() * 8, hipMemcpyHostToDevice, s));
+        if ((rc = setup_render())) return rc;  // (its upload lands before the stream is waited for below)
         {   // the strands' node tables: one launch
             std::vector<TravCtgNodesJob> cj;
             uint32_t max_len = 0;

@@ -3,7 +3,9 @@
 
 #include <functional>
 
+#include <algorithm>
 #include <atomic>
+#include <cassert>
 #include <charconv>
 #include <chrono>
 #include <cstdio>
@@ -14,6 +16,8 @@
 #include <sstream>
 #include <thread>
 #include <vector>
+
+#include <unistd.h>
 
 #include "traversal.hpp"
 
@@ -92,9 +96,19 @@ std::set<std::pair<std::string, bool>> assemble(const std::string &outDir, const
         bool written = true;
         std::FILE *f = nullptr;
         std::atomic<std::size_t> turn{0};
+        // PAGRAPH_DEVICE_DUMPS: the body as the device rendered it (AssembleShare::dumpText) — written in pieces of PIECE bytes
+        // at their offsets behind the header line, by the same pool; such a file has no chunks to render
+        const char *text = nullptr;
+        std::uint64_t textLen = 0, headerLen = 0;
+        std::size_t nPieces = 0;
     };
+    const std::uint64_t PIECE = 8u << 20;
     std::vector<DumpFile> files(ctgList.size());
     std::vector<std::pair<std::size_t, std::size_t>> chunkOf;  // (file, chunk in file)
+    std::vector<std::pair<std::size_t, std::size_t>> pieceOf;  // (file, piece of its device text)
+    std::uint64_t devBytes = 0, devVertices = 0, hostContigs = 0;
+    std::atomic<std::uint64_t> renderNs{0}, writeNs{0};
+    auto nowNs = [] { return static_cast<std::uint64_t>(std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count()); };
     for (std::size_t li = 0; li < ctgList.size(); ++li) {
         DumpFile &F = files[li];
         F.ctgIdx = contigs.id(ctgList[li].first);
@@ -106,6 +120,25 @@ std::set<std::pair<std::string, bool>> assemble(const std::string &outDir, const
         F.nChunks = (res.size() + CHUNK - 1) / CHUNK;
         F.written = !(share && share->writesDump) || share->writesDump(F.ctgIdx);  // (a sharded run: the rank that walked the contig writes its dump)
         if (!F.written) F.nChunks = 0;
+        const std::size_t slot = 2 * F.ctgIdx + F.ctgOffset;
+        // (a text is taken only if it can be the body of these records: one line per record — the shortest line there is has 18
+        // bytes — and a newline at its end; anything else, a stale or mismatched pointer, goes to the host renderer and shows up
+        // in the timing line's count)
+        const char *devText = F.written && !res.empty() && share && share->dumpText && slot < share->dumpText->size() ? (*share->dumpText)[slot].first : nullptr;
+        const std::uint64_t devLen = devText ? (*share->dumpText)[slot].second : 0;
+        if (devText && devLen >= 18 * static_cast<std::uint64_t>(res.size()) && devText[devLen - 1] == '\n') {
+#ifdef PAGH_CHECK_DUMP_TEXT  // (a pass over half a gigabyte per block: for builds that hunt a mismatch, not for the product)
+            assert(static_cast<std::size_t>(std::count(devText, devText + devLen, '\n')) == res.size());
+#endif
+            F.text = devText;
+            F.textLen = devLen;
+            F.nPieces = static_cast<std::size_t>((F.textLen + PIECE - 1) / PIECE);
+            F.nChunks = 0;
+            devBytes += F.textLen;
+            devVertices += res.size();
+        } else if (F.written && !res.empty()) {
+            ++hostContigs;
+        }
     }
     // chunk c of every file before chunk c + 1 of any: the threads then append to as many different files as there are
     // threads (writing new pages of a file is what the kernel serialises)
@@ -114,6 +147,15 @@ std::set<std::pair<std::string, bool>> assemble(const std::string &outDir, const
         for (std::size_t li = 0; li < files.size(); ++li)
             if (c < files[li].nChunks) {
                 chunkOf.emplace_back(li, c);
+                any = true;
+            }
+        if (!any) break;
+    }
+    for (std::size_t c = 0;; ++c) {
+        bool any = false;
+        for (std::size_t li = 0; li < files.size(); ++li)
+            if (c < files[li].nPieces) {
+                pieceOf.emplace_back(li, c);
                 any = true;
             }
         if (!any) break;
@@ -141,16 +183,36 @@ std::set<std::pair<std::string, bool>> assemble(const std::string &outDir, const
             openFailed = true;
             return;
         }
-        std::fprintf(F.f, "%s\t%zu\n", ctgList[li].first.c_str(), static_cast<std::size_t>(contigs.length(F.ctgIdx)));
+        const int hl = std::fprintf(F.f, "%s\t%zu\n", ctgList[li].first.c_str(), static_cast<std::size_t>(contigs.length(F.ctgIdx)));
+        if (F.text && (hl < 0 || std::fflush(F.f) != 0)) openFailed = true;
+        F.headerLen = hl < 0 ? 0 : static_cast<std::uint64_t>(hl);
     });
     if (openFailed) {
         for (auto &F : files)
             if (F.f) std::fclose(F.f);
         throw std::runtime_error("cannot write the path dumps into " + outDir);
     }
-    runPool(chunkOf.size(), [&](std::size_t x) {
+    std::atomic<bool> writeFailed{false};
+    runPool(pieceOf.size() + chunkOf.size(), [&](std::size_t x) {
+        if (x < pieceOf.size()) {  // a piece of a device-rendered body, at its place in the file
+            DumpFile &F = files[pieceOf[x].first];
+            const std::uint64_t from = pieceOf[x].second * PIECE, to = std::min(F.textLen, from + PIECE);
+            const std::uint64_t t0 = timing ? nowNs() : 0;
+            for (std::uint64_t at = from; at < to;) {
+                const ssize_t w = ::pwrite(fileno(F.f), F.text + at, static_cast<std::size_t>(to - at), static_cast<off_t>(F.headerLen + at));
+                if (w <= 0) {
+                    writeFailed = true;
+                    return;
+                }
+                at += static_cast<std::uint64_t>(w);
+            }
+            if (timing) writeNs += nowNs() - t0;
+            return;
+        }
+        x -= pieceOf.size();
         DumpFile &F = files[chunkOf[x].first];
         const std::size_t c = chunkOf[x].second;
+        const std::uint64_t t0 = timing ? nowNs() : 0;
         const auto &res = results[2 * F.ctgIdx + F.ctgOffset];
         const std::size_t from = c * CHUNK, to = std::min(res.size(), from + CHUNK);
         SeqTools algo(graph, contigs, refs, ctgMapper, refMapper);
@@ -180,13 +242,29 @@ std::set<std::pair<std::string, bool>> assemble(const std::string &outDir, const
             putInt(d2.second);
             buf.push_back('\n');
         }
+        const std::uint64_t t1 = timing ? nowNs() : 0;
         while (F.turn.load(std::memory_order_acquire) != c) std::this_thread::yield();
         std::fwrite(buf.data(), 1, buf.size(), F.f);
         F.turn.store(c + 1, std::memory_order_release);
+        if (timing) renderNs += t1 - t0, writeNs += nowNs() - t1;
     });
     for (std::size_t li = 0; li < ctgList.size(); ++li) {
         DumpFile &F = files[li];
         if (F.f) std::fclose(F.f);
+    }
+    if (writeFailed) throw std::runtime_error("cannot write the path dumps into " + outDir);
+    if (timing) {
+        // (render / write: time of the pool's threads, summed — the host's formatting of the contigs without a device text, and
+        // the fwrite / pwrite calls including a chunk's wait for its turn; wall: this lap so far)
+        std::uint64_t hostVertices = 0;
+        for (auto &pr : chunkOf) {
+            const DumpFile &F = files[pr.first];
+            const std::size_t sz = results[2 * F.ctgIdx + F.ctgOffset].size();
+            hostVertices += std::min(sz, (pr.second + 1) * CHUNK) - pr.second * CHUNK;
+        }
+        std::fprintf(stderr, "[timing] path dumps: device-rendered %llu bytes %llu vertices; host-rendered %llu contigs %llu vertices; render %.1f ms write %.1f ms (thread time) wall %.1f ms\n",
+                     (unsigned long long)devBytes, (unsigned long long)devVertices, (unsigned long long)hostContigs, (unsigned long long)hostVertices,
+                     renderNs.load() * 1e-6, writeNs.load() * 1e-6, nowMs() - tLap);
     }
     if (share && share->dumpsOnly) {
         lap("per-contig dumps of this rank's contigs");

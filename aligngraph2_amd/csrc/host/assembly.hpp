@@ -31,9 +31,14 @@ struct AssembleStats {
 // contigs IT walked, from its own travel sequences — the dumps are most of a block's output bytes; the chain selection and
 // everything after it needs all travel sequences and stays with rank 0.  writesDump(contig id): does this call write that
 // contig's dump; dumpsOnly: return after the dumps (a rank other than 0: ctgSet = its own contigs, the result is empty).
+// dumpText (PAGRAPH_DEVICE_DUMPS): the body of a dump as the device rendered it from the travel sequence of that slot
+// (2 * contig + (reverse ? 1 : 0); {nullptr, 0}: none) — written behind the header line as it is; a contig without one is
+// rendered by the host threads.
+using DumpTexts = std::vector<std::pair<const char *, std::uint64_t>>;
 struct AssembleShare {
     std::function<bool(std::size_t)> writesDump;
     bool dumpsOnly = false;
+    const DumpTexts *dumpText = nullptr;
 };
 std::set<std::pair<std::string, bool>> assemble(const std::string &outDir, const std::string &prefix, const HostGraph &graph,
                                                 const SeqDb &contigs, const SeqDb &refs, const PositionMapper &ctgMapper,

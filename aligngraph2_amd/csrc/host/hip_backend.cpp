@@ -109,7 +109,9 @@ public:
         }
         buildPathGraph(tv.views, ctx.k, graph, travelled);
         gathered_.swap(tv.gathered);  // (the path graph refers to it)
+        texts_.swap(tv.texts);
     }
+    const std::vector<std::pair<const char *, std::uint64_t>> *travelDumpTexts() const override { return texts_.empty() ? nullptr : &texts_; }
 
     bool travelsInHalves() const override { return true; }
 
@@ -144,15 +146,24 @@ public:
         std::vector<std::uint32_t> refLen;
         for (std::size_t i = 0; i < ctx.refs.size(); ++i) refLen.push_back(ctx.refs.length(i));
         pag_seqs cs{contigs.size(), contigs.byteOff().data(), contigs.lens().data(), contigs.packed().data(), contigs.packed().size()};
-        check(pag_travel(g_, &cs, orient.data(), refLen.data(), refLen.size(), &params, nullptr), "pag_travel");
+        pag_travel_params asked = params;
+        if (envDeviceDumps()) asked.reserved |= PAG_TRAVEL_RENDER_DUMPS;
+        check(pag_travel(g_, &cs, orient.data(), refLen.data(), refLen.size(), &asked, nullptr), "pag_travel");
         std::vector<std::pair<const pag_path_node *, std::uint64_t>> &views = out.views;
         std::vector<char> &gathered = out.gathered;
         views.assign(2 * contigs.size(), {nullptr, 0});
+        out.texts.clear();
+        if (envDeviceDumps()) out.texts.assign(2 * contigs.size(), {nullptr, 0});
         for (std::uint64_t c = 0; c < contigs.size(); ++c)
             for (int rev = 0; rev < 2; ++rev) {
                 std::uint64_t len = 0;
                 const pag_path_node *p = pag_travel_path_oriented(g_, c, rev == 0, &len);
                 if (p && len) views[2 * c + rev] = {p, len};
+                if (p && len && envDeviceDumps()) {
+                    std::uint64_t bytes = 0;
+                    const char *t = pag_travel_dump_text(g_, c, rev == 0, &bytes);
+                    if (t && bytes) out.texts[2 * c + rev] = {t, bytes};
+                }
             }
         if (comm_) {
             // the travel sequences of all ranks to rank 0 (which selects the chains and writes the block's outputs):
@@ -217,6 +228,7 @@ private:
     pag_comm *comm_ = nullptr;
     unsigned rank_ = 0, world_ = 1;
     ShardPlan plan_;
+    std::vector<std::pair<const char *, std::uint64_t>> texts_;  // PAGRAPH_DEVICE_DUMPS: the dump bodies of the last travel()
     std::vector<char> gathered_;  // rank 0: the travel sequences of all ranks (the path graph refers to them)
 };
 

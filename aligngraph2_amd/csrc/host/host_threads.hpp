@@ -17,6 +17,12 @@ inline long long envInt(const char *name, long long otherwise) {
 }
 // PAGRAPH_TIMING: lap timers of the host stages on stderr
 inline bool envTiming() { return std::getenv("PAGRAPH_TIMING") != nullptr; }
+// PAGRAPH_DEVICE_DUMPS=1: the bodies of the per-contig path dumps are rendered on the device while the walks deliver the
+// paths (pag_travel, PAG_TRAVEL_RENDER_DUMPS) and written out as they come; read once.  Unset: the host renders them.
+inline bool envDeviceDumps() {
+    static const bool on = envInt("PAGRAPH_DEVICE_DUMPS", 0) == 1;
+    return on;
+}
 // PAGH_OVERLAP_THREADS=<n>: host threads of a block's host half while it runs beside the next block's device work (0: not given)
 inline unsigned envOverlapThreads() {
     const char *e = std::getenv("PAGH_OVERLAP_THREADS");

@@ -377,8 +377,10 @@ int runPagraph(int argc, char **argv, GraphBackend &backend) {
                     ++blockNo;
                     continue;
                 }
+                AssembleShare share;
+                share.dumpText = backend.travelDumpTexts();
                 auto successCtg = assemble(opt.out, prefix, graphs[0], contigs, refs, ctgMapper, refMapper, usedCtg, opt.epsilon * 2, errorRate,
-                                           startSplit, opt.minLen, opt.threads, 0, nullptr, false, precomputed[0]);
+                                           startSplit, opt.minLen, opt.threads, 0, nullptr, false, precomputed[0], nullptr, share.dumpText ? &share : nullptr);
                 lap("traverse + write");
                 ++blockNo;
                 for (auto &s : successCtg) okCtg.emplace(s.first);
@@ -407,6 +409,7 @@ int runPagraph(int argc, char **argv, GraphBackend &backend) {
                         buildPathGraph(tviews[slot].views, static_cast<unsigned>(kmers.k()), graphs[slot], precomputed[slot]);
                         AssembleShare share;
                         share.dumpsOnly = true;
+                        if (!tviews[slot].texts.empty()) share.dumpText = &tviews[slot].texts;
                         assemble(opt.out, prefix, graphs[slot], contigs, refs, cm, rm, own, opt.epsilon * 2, errorRate, startSplit, opt.minLen, opt.threads, 0,
                                  nullptr, true, precomputed[slot], nullptr, &share);
                         lap("path dumps of this rank's contigs");
@@ -432,8 +435,10 @@ int runPagraph(int argc, char **argv, GraphBackend &backend) {
                     buildPathGraph(tviews[slot].views, static_cast<unsigned>(kmers.k()), graphs[slot], precomputed[slot]);
                     AssembleShare share;
                     if (rankDumps) share.writesDump = [&walkedHere](std::size_t id) { return id < walkedHere.size() && walkedHere[id] != 0; };
+                    // (the text lives as long as the travel sequences: until the walks of the block after this one, which wait for this thread)
+                    if (!tviews[slot].texts.empty()) share.dumpText = &tviews[slot].texts;
                     return assemble(opt.out, prefix, graphs[slot], contigs, refs, cm, rm, usedCtg, opt.epsilon * 2, errorRate, startSplit, opt.minLen,
-                                    opt.threads, poolThreads, nullptr, false, precomputed[slot], &half.log, rankDumps ? &share : nullptr);
+                                    opt.threads, poolThreads, nullptr, false, precomputed[slot], &half.log, rankDumps || share.dumpText ? &share : nullptr);
                 });
                 ++blockNo;
             }

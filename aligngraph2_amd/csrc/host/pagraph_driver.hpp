@@ -62,7 +62,10 @@ public:
     struct TravelViews {
         std::vector<std::pair<const pag_path_node *, std::uint64_t>> views;  // 2 * contig + (reverse ? 1 : 0)
         std::vector<char> gathered;                                          // (a sharded run: what the other ranks sent)
+        std::vector<std::pair<const char *, std::uint64_t>> texts;           // PAGRAPH_DEVICE_DUMPS: dump bodies of the contigs walked here
     };
+    // PAGRAPH_DEVICE_DUMPS: the dump bodies the last travel() left (null: none; valid until the next travel)
+    virtual const std::vector<std::pair<const char *, std::uint64_t>> *travelDumpTexts() const { return nullptr; }
     virtual bool travelsInHalves() const { return false; }
     virtual void travelPrepare(const TravelContext &, const pag_travel_params &) {}
     virtual void travelWalks(const TravelContext &, const pag_travel_params &, TravelViews &) {}

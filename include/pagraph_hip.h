@@ -414,6 +414,30 @@ const pag_path_node *pag_travel_path_oriented(const pag_graph *g, uint64_t ctg_i
  * parses its inputs (no other call on the handle may run at the same time): a first large allocation of a process can take
  * seconds.  pag_travel sizes the arena itself when this was not called or asked for too little. */
 int pag_reserve_walk_arena(pag_graph *g, uint64_t contig_bases);
+/* ---- the per-contig path dumps as text, rendered on the device (csrc/hip/k5_dump.hip) ------------------------------------
+ * The body of a dump file (<prefix><contig>_<0|1>.txt, PAssembly.cpp:47-60) is one line per path vertex, in path order:
+ *     <KMER>,<ctg>,<ref>,<cnt>\t<step>\t<cIdx>,<cOff>\t<rIdx>,<rOff>\n
+ * KMER = the k bases of `code`, first base most significant; ctg / ref unsigned; cnt the u16; step signed; (cIdx, cOff) /
+ * (rIdx, rOff) = PositionMapper::singleToDual (PositionMapper.cpp:44-70) of ctg / ref over the contigs / the references, signed.
+ * A coordinate at or past the end of its space is given the index -(n + 1) (the reference reads past its size table there).
+ * Both coordinate spaces must fit 32 bits (as the single coordinates do) and hold at most 99 999 999 sequences.
+ *
+ * pag_render_dump_lines: the body for n records in HOST memory into the caller's buffer.  *bytes always receives the size
+ * the text takes; PAG_ERANGE when cap is smaller (nothing is written then), PAG_EINVAL for k outside 1..16 or tables out of
+ * bounds, PAG_ENODEV without a gfx950 device (no host fallback behind this call).  A utility entry point, not a hot path: every
+ * call creates and destroys a stream and its device buffers (records, tables, tile counters, text) on `device` and waits for
+ * the result; the calling thread's current device is the same after the call as before it.
+ *
+ * pag_travel with PAG_TRAVEL_RENDER_DUMPS set in pag_travel_params.reserved renders the body for every contig it delivers,
+ * from the records pag_travel_path_oriented returns for it and 1:1 with them; pag_travel_dump_text(g, i, forward, &bytes)
+ * returns that text: library-owned PINNED memory with the lifetime of those records (valid until the next pag_travel or
+ * pag_destroy on the handle).  NULL / 0: the orientation was not traversed, its path is empty, rendering was not asked for,
+ * or the text could not be rendered (tables out of bounds, no room in the walk arena, a line longer than paths' vertices
+ * produce) — the caller then formats the records itself. */
+#define PAG_TRAVEL_RENDER_DUMPS 1u
+int pag_render_dump_lines(const pag_path_node *records, uint64_t n, uint32_t k, const uint32_t *ctg_len, uint64_t n_ctgs,
+                          const uint32_t *ref_len, uint64_t n_refs, char *out, uint64_t cap, uint64_t *bytes, int device);
+const char *pag_travel_dump_text(const pag_graph *g, uint64_t ctg_index, int forward, uint64_t *bytes);
 /* ---- kmer_counter on the device (replaces PAGraph/src/main/kmer_counter.cpp:19-96) ----------------
  * Counts every k-mer of the forward strand of every read (KmerHelper::kmer2Code, KmerHelper.cpp:7-25) in a dense 4^k
  * table, derives the minimum abundance by the reference's rule (the first occurring abundance a, ascending, with

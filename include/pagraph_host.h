@@ -56,6 +56,16 @@ int pagh_assemble_paths(pag_graph *cache_key, uint32_t k, const pag_seqs *ctgs, 
                         const pag_path_node *const *paths, const uint64_t *path_len, uint32_t ref_threads, uint64_t epsilon,
                         uint64_t min_len, const char *out_dir, const char *prefix, uint32_t host_threads,
                         pagh_traverse_stats *stats);
+/* ... with the bodies of the path dumps already rendered (pag_travel with PAG_TRAVEL_RENDER_DUMPS, pag_travel_dump_text):
+ * dump_text[2 * c + (reverse ? 1 : 0)] / dump_text_len[...] = the text that belongs to paths[...] (NULL / 0: none — the host
+ * renders that contig's lines itself).  A dump file then is its header line followed by that buffer as it is.  dump_text NULL:
+ * pagh_assemble_paths.  pagh_traverse* ask for the text and pass it on when PAGRAPH_DEVICE_DUMPS=1 is in the environment
+ * (read once); the files are the same bytes either way. */
+int pagh_assemble_paths_text(pag_graph *cache_key, uint32_t k, const pag_seqs *ctgs, const char *const *ctg_names,
+                             const pag_seqs *refs, const char *const *ref_names, const int32_t *ctg_orient,
+                             const pag_path_node *const *paths, const uint64_t *path_len, const char *const *dump_text,
+                             const uint64_t *dump_text_len, uint32_t ref_threads, uint64_t epsilon, uint64_t min_len,
+                             const char *out_dir, const char *prefix, uint32_t host_threads, pagh_traverse_stats *stats);
 /* Drops the host storage kept for a graph handle between pagh_traverse calls; waits for a host half still running.  Call it
  * before pag_destroy of a handle that was traversed. */
 void pagh_release(pag_graph *g);
