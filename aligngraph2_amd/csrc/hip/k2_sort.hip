@@ -377,9 +377,9 @@ int sort_pairs(uint32_t *k0, uint64_t *v0, uint32_t *k1, uint64_t *v1, uint64_t 
     // synchronisation their reading takes.  A caller that does not ask gets neither — until round 5 every call created and
     // destroyed 2 x passes events and synchronised the stream.
     const bool timed = ms_dominant_kernel != nullptr;
-    static thread_local hipEvent_t ev_pool[64][2 * 8];  // (per host thread: two handles of one device may sort at the same time)
+    static thread_local hipEvent_t ev_sets[64][2 * 8];  // (per host thread: two handles of one device may sort at the same time)
     static thread_local bool ev_ready[64] = {false};
-    hipEvent_t *ev = ev_pool[dev & 63];
+    hipEvent_t *ev = ev_sets[dev & 63];
     if (timed && !ev_ready[dev & 63]) {
         for (int i = 0; i < 2 * 8; ++i) PAG_HIP_TRY(hipEventCreate(&ev[i]));
         ev_ready[dev & 63] = true;

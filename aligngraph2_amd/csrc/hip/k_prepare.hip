@@ -33,7 +33,6 @@ namespace pagdev {
 
 namespace {
 
-constexpr int PREP_SLOT0 = 128;  // pool slots of this stage
 constexpr uint32_t LIST_INSERTION_MAX = 16;  // libstdc++ _S_threshold: std::sort of <= 16 elements is __insertion_sort
 
 __device__ __forceinline__ void d_flip(uint64_t &left, uint64_t &right, uint64_t length) {  // Aligner::flipPosition (Aligner.cpp:235-239)
@@ -404,15 +403,15 @@ std::vector<uint64_t> mapper_starts(const uint32_t *len, uint64_t n) {
 }
 
 // the lists of one read database -> compacted pag_aln records + query_off (device)
-int prepare_read_db(pag_graph *g, int pass, const pag_raw_db &db, const uint32_t *d_diff, PrepTables T, int slot0, pag_aln_db *out,
+int prepare_read_db(pag_graph *g, int pass, const pag_raw_db &db, const uint32_t *d_diff, PrepTables T, pag_aln_db *out,
                     uint32_t *d_err) {
     hipStream_t s = g->stream;
     const uint64_t n = db.n;
     const uint32_t nq = T.n_reads;
-    int slot = slot0;
-    DevBuf b_rec(g, slot++), b_k0(g, slot++), b_v0(g, slot++), b_k1(g, slot++), b_v1(g, slot++), b_tmp(g, slot++), b_off(g, slot++),
-        b_long(g, slot++), b_alnt(g, slot++), b_keep(g, slot++), b_pos(g, slot++), b_aln(g, slot++), b_qoff(g, slot++), b_inl(g, slot++),
-        b_pos2(g, slot++);
+    auto buf = [&](ps::PrepDbBuf b) { return DevBuf(g, ps::prep_db(pass, b)); };
+    DevBuf b_rec = buf(ps::DB_REC), b_k0 = buf(ps::DB_K0), b_v0 = buf(ps::DB_V0), b_k1 = buf(ps::DB_K1), b_v1 = buf(ps::DB_V1), b_tmp = buf(ps::DB_TMP),
+           b_off = buf(ps::DB_OFF), b_long = buf(ps::DB_LONG), b_alnt = buf(ps::DB_ALNT), b_keep = buf(ps::DB_KEEP), b_pos = buf(ps::DB_POS),
+           b_aln = buf(ps::DB_ALN), b_qoff = buf(ps::DB_QOFF), b_inl = buf(ps::DB_INL), b_pos2 = buf(ps::DB_POS2);
     int rc;
     if ((rc = b_rec.alloc((n + 1) * sizeof(pag_raw_aln))) || (rc = b_k0.alloc((n + 1) * 4)) || (rc = b_v0.alloc((n + 1) * 8)) ||
         (rc = b_k1.alloc((n + 1) * 4)) || (rc = b_v1.alloc((n + 1) * 8)) ||
@@ -537,12 +536,11 @@ extern "C" int pag_prepare(pag_graph *g, const pag_raw_input *raw, pag_build_inp
         return PAG_EINVAL;
     }
     int rc;
-    int slot = PREP_SLOT0;
-    DevBuf b_roff(g, slot++), b_rlen(g, slot++), b_packed(g, slot++), b_d1(g, slot++), b_d2(g, slot++), b_d3(g, slot++), b_clen(g, slot++),
-        b_csel(g, slot++), b_cfwd(g, slot++), b_rflen(g, slot++), b_racc(g, slot++), b_ctab(g, slot++), b_rtab(g, slot++), b_order(g, slot++),
-        b_err(g, slot++), b_jobs(g, slot++), b_cfirst(g, slot++), b_pre(g, slot++), b_cnt(g, slot++), b_multi(g, slot++), b_isend(g, slot++),
-        b_run(g, slot++), b_scan(g, slot++), b_stmp(g, slot++), b_eoff(g, slot++), b_ent(g, slot++), b_ends(g, slot++);
-    const int SLOT_DB1 = slot, SLOT_DB2 = slot + 16;
+    DevBuf b_roff(g, ps::PREP_ROFF), b_rlen(g, ps::PREP_RLEN), b_packed(g, ps::PREP_PACKED), b_d1(g, ps::PREP_D1), b_d2(g, ps::PREP_D2), b_d3(g, ps::PREP_D3),
+        b_clen(g, ps::PREP_CLEN), b_csel(g, ps::PREP_CSEL), b_cfwd(g, ps::PREP_CFWD), b_rflen(g, ps::PREP_RFLEN), b_racc(g, ps::PREP_RACC),
+        b_ctab(g, ps::PREP_CTAB), b_rtab(g, ps::PREP_RTAB), b_order(g, ps::PREP_ORDER), b_err(g, ps::PREP_ERR), b_jobs(g, ps::PREP_JOBS),
+        b_cfirst(g, ps::PREP_CFIRST), b_pre(g, ps::PREP_PRE), b_cnt(g, ps::PREP_CNT), b_multi(g, ps::PREP_MULTI), b_isend(g, ps::PREP_ISEND),
+        b_run(g, ps::PREP_RUN), b_scan(g, ps::PREP_SCAN), b_stmp(g, ps::PREP_STMP), b_eoff(g, ps::PREP_EOFF), b_ent(g, ps::PREP_ENT), b_ends(g, ps::PREP_ENDS);
     auto put = [&](DevBuf &b, const void *src, size_t bytes, bool on_dev, const void **dst) -> int {
         if (on_dev) {
             *dst = src;
@@ -704,9 +702,9 @@ extern "C" int pag_prepare(pag_graph *g, const pag_raw_input *raw, pag_build_inp
     T.n_refs = (uint32_t)n_refs;
     pag_build_input o{};
     T.ratio = raw->read_to_ctg_ratio;
-    if ((rc = prepare_read_db(g, 0, raw->read_to_ctg, (const uint32_t *)d_d1, T, SLOT_DB1, &o.read_to_ctg, b_err.as<uint32_t>()))) return rc;
+    if ((rc = prepare_read_db(g, 0, raw->read_to_ctg, (const uint32_t *)d_d1, T, &o.read_to_ctg, b_err.as<uint32_t>()))) return rc;
     T.ratio = raw->read_to_ref_ratio;
-    if ((rc = prepare_read_db(g, 1, raw->read_to_ref, (const uint32_t *)d_d2, T, SLOT_DB2, &o.read_to_ref, b_err.as<uint32_t>()))) return rc;
+    if ((rc = prepare_read_db(g, 1, raw->read_to_ref, (const uint32_t *)d_d2, T, &o.read_to_ref, b_err.as<uint32_t>()))) return rc;
 
     // ---- emission order
     if ((rc = b_order.alloc((n_reads + 1) * 4))) return rc;

@@ -22,8 +22,6 @@
 namespace pagdev {
 namespace {
 
-constexpr int SEL_SLOT0 = 192;
-
 __device__ __forceinline__ bool in_intervals(const uint32_t *__restrict__ iv, uint32_t n, uint32_t x) {
     if (!n) return false;
     uint32_t lo = 0, hi = n;  // last interval with lo <= x
@@ -117,9 +115,12 @@ extern "C" int pag_shard_select(pag_graph *g, const pag_region *r, pag_shard_sli
     hipStream_t s = g->stream;
     const uint64_t T = g->n_t, E = g->n_e;
     const uint64_t n_words = ((1ull << (2 * g->k)) + 63) / 64;
-    int rc, slot = SEL_SLOT0;
-    DevBuf b_civ(g, slot++), b_riv(g, slot++), b_keep(g, slot++), b_pos(g, slot++), b_codes(g, slot++), b_tmp(g, slot++), b_cnt(g, slot++), b_tk(g, slot++),
-        b_tv(g, slot++), b_ts(g, slot++), b_tc(g, slot++), b_ek(g, slot++), b_ev(g, slot++), b_es(g, slot++);
+    int rc;
+    DevBuf b_civ(g, ps::SEL_CIV), b_riv(g, ps::SEL_RIV), b_keep(g, ps::SEL_KEEP), b_pos(g, ps::SEL_POS), b_codes(g, ps::SEL_CODES), b_tmp(g, ps::SEL_TMP),
+        b_cnt(g, ps::SEL_CNT);
+    auto out_buf = [&](ps::GraphArr a) { return DevBuf(g, ps::family(ps::SEL_OUT, a)); };
+    DevBuf b_tk = out_buf(ps::G_TKEY), b_tv = out_buf(ps::G_TVAL), b_ts = out_buf(ps::G_TSEG), b_tc = out_buf(ps::G_TCNT), b_ek = out_buf(ps::G_EKEY),
+           b_ev = out_buf(ps::G_EVAL), b_es = out_buf(ps::G_ESEG);
     const uint64_t M = std::max(T, E);
     if ((rc = b_civ.alloc(r->n_ctg_iv * 8 + 16)) || (rc = b_riv.alloc(r->n_ref_iv * 8 + 16)) || (rc = b_keep.alloc((M + 2) * 4)) ||
         (rc = b_pos.alloc((M + 3) * 8)) || (rc = b_codes.alloc(n_words * 8)) || (rc = b_tmp.alloc(scan_tmp_bytes(M + 2) + 64)) || (rc = b_cnt.alloc(64)))
@@ -154,13 +155,7 @@ extern "C" int pag_shard_select(pag_graph *g, const pag_region *r, pag_shard_sli
     *out = pag_shard_slice{};
     out->n_t = n_pos;
     out->n_e = n_edges;
-    out->tkey = b_tk.as<uint32_t>();
-    out->tval = b_tv.as<uint64_t>();
-    out->tseg = b_ts.as<uint32_t>();
-    out->tcnt = b_tc.as<uint16_t>();
-    out->ekey = b_ek.as<uint32_t>();
-    out->eval = b_ev.as<uint64_t>();
-    out->eseg = b_es.as<uint32_t>();
+    point_at(*out, arrays_in(g, ps::SEL_OUT));
     out->stats = g->stats;  // the owner's share of the count lines ...
     out->stats.n_nodes = n_nodes;  // ... and what of its slice goes to this rank
     out->stats.n_pos = n_pos;
@@ -178,25 +173,20 @@ extern "C" int pag_shard_set_region(pag_graph *g, const pag_region *r) {
     return PAG_OK;
 }
 
-// The build stages' device memory (inputs, tuple streams, sort and segment scratch, the owner's slice, the selections:
-// pool slots 0 .. 51 and 192 ..) handed back once the rank has imported its region: at BASELINE configs[2] that is ~70 GB
-// per GPU the traversal needs.  The imported graph (slots 52 .. 58) and the traversal's slots stay.
+// The device memory of the preparation, the build (inputs, tuple streams, sort and segment scratch, the owner's slice), the
+// selections and the exchange (ps::released_after_import) handed back once the rank has imported its region: at BASELINE
+// configs[2] that is ~70 GB per GPU the traversal needs.  The imported graph and the traversal's slots stay.
 extern "C" int pag_shard_release_build(pag_graph *g) {
     if (!g) return PAG_EINVAL;
     PAG_HIP_TRY(hipSetDevice(g->device));
     PAG_HIP_TRY(hipStreamSynchronize(g->stream));
-    auto drop = [&](int a, int b) {
-        for (int i = a; i < b; ++i) {
-            pag_graph::Slot &sl = g->pool[i];
-            if (sl.p && sl.p != (void *)g->tkey && sl.p != (void *)g->tval && sl.p != (void *)g->tseg && sl.p != (void *)g->tcnt && sl.p != (void *)g->ekey &&
-                sl.p != (void *)g->eval && sl.p != (void *)g->eseg) {
-                hipFree(sl.p);
-                sl.p = nullptr;
-                sl.cap = 0;
-            }
-        }
-    };
-    drop(0, 52);
-    drop(128, 256);
+    const GraphArrays held = arrays_of(*g);  // (what the handle's graph still points at stays)
+    for (int i = 0; i < ps::COUNT; ++i) {
+        pag_graph::Slot &sl = g->pool[i];
+        if (!ps::released_after_import((ps::Id)i) || !sl.p || std::find(held.p, held.p + ps::GRAPH_ARRS, sl.p) != held.p + ps::GRAPH_ARRS) continue;
+        hipFree(sl.p);
+        sl.p = nullptr;
+        sl.cap = 0;
+    }
     return PAG_OK;
 }

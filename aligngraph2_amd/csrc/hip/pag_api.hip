@@ -282,13 +282,30 @@ int pag_reset(pag_graph *g) {
 
 namespace {
 
-struct Extracted {  // what extract_stage leaves in the pool slots 30 / 31 / 34 / 35
+struct Extracted {  // what extract_stage leaves in the stream slots (ps::TK0 / TV0 / EK0 / EV0)
     uint64_t T = 0, E = 0, T1 = 0, E1 = 0;  // tuples / edges emitted, of which by pass 1 (they come first)
+};
+
+// What a sort of the streams works on (build_stage: K2; pag_shard_extract_range: the owner partition): the stream slots, which
+// the caller has filled (alloc() only hands their pointers back), their ping-pong partners and the sort scratch, for T tuples
+// and E edges.  The second value buffer of each stream doubles as u64[n] + u32[n] scratch for long segments.
+struct StreamBufs {
+    DevBuf tk0, tv0, tk1, tv1, ek0, ev0, ek1, ev1, sorttmp;
+    explicit StreamBufs(pag_graph *g)
+        : tk0(g, ps::TK0), tv0(g, ps::TV0), tk1(g, ps::TK1), tv1(g, ps::TV1), ek0(g, ps::EK0), ev0(g, ps::EV0), ek1(g, ps::EK1), ev1(g, ps::EV1),
+          sorttmp(g, ps::SORT_TMP) {}
+    int alloc(uint64_t T, uint64_t E) {
+        int rc;
+        if ((rc = tk0.alloc((T + 1) * 4)) || (rc = tv0.alloc((T + 1) * 8)) || (rc = ek0.alloc((E + 1) * 4)) || (rc = ev0.alloc((E + 1) * 8)) ||
+            (rc = tk1.alloc((T + 1) * 4)) || (rc = tv1.alloc((T + 1) * 12)) || (rc = ek1.alloc((E + 1) * 4)) || (rc = ev1.alloc((E + 1) * 12)))
+            return rc;
+        return sorttmp.alloc(sort_tmp_bytes(std::max(T, E)));
+    }
 };
 
 // Both extraction passes of PositionProcessor::process (PositionProcessor.cpp:86-124) for the reads at emission positions
 // [emit_lo, emit_hi) of in->emit_order: coverage filter, column index, K1 count, scans, K1 emit.  The streams
-// [pass-1 tuples] ++ [pass-2 tuples] (and edges likewise) are left in canonical order in slots 30/31 (tuples) and 34/35 (edges).
+// [pass-1 tuples] ++ [pass-2 tuples] (and edges likewise) are left in canonical order in the stream slots.
 int extract_stage(pag_graph *g, const pag_build_input *in, uint64_t emit_lo, uint64_t emit_hi, Extracted *out, hipEvent_t ev_begin,
                   hipEvent_t ev_end) {
     hipStream_t s = g->stream;
@@ -300,7 +317,9 @@ int extract_stage(pag_graph *g, const pag_build_input *in, uint64_t emit_lo, uin
     if (ev_begin) PAG_HIP_TRY(hipEventRecord(ev_begin, s));
 
     // ---- inputs -> device
-    DevBuf b_roff(g, 0), b_rlen(g, 1), b_packed(g, 2), b_order(g, 3), b_aln1(g, 4), b_q1(g, 5), b_d1(g, 6), b_aln2(g, 7), b_q2(g, 8), b_d2(g, 9), b_ctg(g, 10), b_eoff(g, 11), b_ent(g, 12), b_ref(g, 13);
+    DevBuf b_roff(g, ps::IN_ROFF), b_rlen(g, ps::IN_RLEN), b_packed(g, ps::IN_PACKED), b_order(g, ps::IN_ORDER), b_aln1(g, ps::IN_ALN1), b_q1(g, ps::IN_Q1),
+        b_d1(g, ps::IN_D1), b_aln2(g, ps::IN_ALN2), b_q2(g, ps::IN_Q2), b_d2(g, ps::IN_D2), b_ctg(g, ps::IN_CTG), b_eoff(g, ps::IN_EOFF), b_ent(g, ps::IN_ENT),
+        b_ref(g, ps::IN_REF);
     const uint64_t *d_roff;
     const uint32_t *d_rlen, *d_order, *d_d1, *d_d2, *d_eoff, *d_ent;
     const uint8_t *d_packed;
@@ -333,7 +352,7 @@ int extract_stage(pag_graph *g, const pag_build_input *in, uint64_t emit_lo, uin
 
     // ---- coverage filter of pass 2 (over ALL read->reference alignments, whichever reads this call extracts)
     const uint64_t n_aln1 = in->read_to_ctg.n_aln, n_aln2 = in->read_to_ref.n_aln;
-    DevBuf b_covok(g, 14), b_covtmp(g, 15);
+    DevBuf b_covok(g, ps::COV_OK), b_covtmp(g, ps::COV_TMP);
     if ((rc = b_covok.alloc(n_aln2 + 16))) return rc;
     size_t cov_bytes = cov_tmp_bytes(refs_host.data(), in->n_refs);
     if ((rc = b_covtmp.alloc(cov_bytes))) return rc;
@@ -342,7 +361,7 @@ int extract_stage(pag_graph *g, const pag_build_input *in, uint64_t emit_lo, uin
         return rc;
 
     // ---- column index of both alignment databases
-    DevBuf b_cc(g, 16), b_cio1(g, 17), b_cio2(g, 18), b_ci1(g, 19), b_ci2(g, 20), b_scan(g, 21), b_tot(g, 22);
+    DevBuf b_cc(g, ps::CI_CC), b_cio1(g, ps::CI_OFF1), b_cio2(g, ps::CI_OFF2), b_ci1(g, ps::CI_1), b_ci2(g, ps::CI_2), b_scan(g, ps::X_SCAN), b_tot(g, ps::X_TOT);
     uint64_t n_alnmax = std::max(n_aln1, n_aln2);
     if ((rc = b_cc.alloc((n_alnmax + 1) * 4))) return rc;
     if ((rc = b_cio1.alloc((n_aln1 + 1) * 8))) return rc;
@@ -372,13 +391,13 @@ int extract_stage(pag_graph *g, const pag_build_input *in, uint64_t emit_lo, uin
     }
 
     // ---- K1 count
-    DevBuf b_js(g, 25), b_jt(g, 26), b_je(g, 27), b_toff(g, 28), b_eoff2(g, 29);
+    DevBuf b_js(g, ps::K1_JS), b_jt(g, ps::K1_JT), b_je(g, ps::K1_JE), b_toff(g, ps::K1_TOFF), b_eoff2(g, ps::K1_EOFF);
     if ((rc = b_js.alloc((n_jobs + 1) * 4))) return rc;
     if ((rc = b_jt.alloc((n_jobs + 1) * 4))) return rc;
     if ((rc = b_je.alloc((n_jobs + 1) * 4))) return rc;
     if ((rc = b_toff.alloc((n_jobs + 1) * 8))) return rc;
     if ((rc = b_eoff2.alloc((n_jobs + 1) * 8))) return rc;
-    DevBuf b_smask(g, 51);
+    DevBuf b_smask(g, ps::SOLID_MASK);
     if (!g->all_solid) {
         // mask entries: 2 strands x one u16 per 16 bases (= per packed 32-bit word of the reads)
         if ((rc = b_smask.alloc((in->reads.packed_bytes / 4 + 16) * 2 * sizeof(uint16_t) * solid_mask_slices()))) return rc;
@@ -415,7 +434,7 @@ int extract_stage(pag_graph *g, const pag_build_input *in, uint64_t emit_lo, uin
         a.job_base = (uint32_t)(pass * 2ull * n_reads);
     }
     // the order pass 0's jobs run in
-    DevBuf b_pk0(g, 39), b_pv0(g, 40), b_pk1(g, 41), b_pv1(g, 42), b_ptmp(g, 23), b_perm(g, 24);
+    DevBuf b_pk0(g, ps::K1_PK0), b_pv0(g, ps::K1_PV0), b_pk1(g, ps::K1_PK1), b_pv1(g, ps::K1_PV1), b_ptmp(g, ps::K1_PTMP), b_perm(g, ps::K1_PERM);
     {
         const uint64_t nj0 = 2ull * n_reads;
         if (nj0 >= 4096) {
@@ -445,11 +464,8 @@ int extract_stage(pag_graph *g, const pag_build_input *in, uint64_t emit_lo, uin
     }
 
     // ---- K1 emit
-    DevBuf b_tk0(g, 30), b_tv0(g, 31), b_ek0(g, 34), b_ev0(g, 35);
-    if ((rc = b_tk0.alloc((T + 1) * 4))) return rc;
-    if ((rc = b_tv0.alloc((T + 1) * 8))) return rc;
-    if ((rc = b_ek0.alloc((E + 1) * 4))) return rc;
-    if ((rc = b_ev0.alloc((E + 1) * 8))) return rc;
+    DevBuf b_tk0(g, ps::TK0), b_tv0(g, ps::TV0), b_ek0(g, ps::EK0), b_ev0(g, ps::EV0);
+    if ((rc = b_tk0.alloc((T + 1) * 4)) || (rc = b_tv0.alloc((T + 1) * 8)) || (rc = b_ek0.alloc((E + 1) * 4)) || (rc = b_ev0.alloc((E + 1) * 8))) return rc;
     for (int pass = 0; pass < 2; ++pass) {
         ExtractArgs &a = xa[pass];
         a.tuple_off = b_toff.as<uint64_t>();
@@ -469,57 +485,49 @@ int extract_stage(pag_graph *g, const pag_build_input *in, uint64_t emit_lo, uin
 }
 
 // mergeEdge / mergeKmerPosition / sortKmerPosition for both passes at once (see the head of this file) over the streams in
-// slots 30/31 (tuples: T records, the first T1 from pass 1) and 34/35 (edges): K2 sorts, K3, K4; leaves the finished graph
+// the stream slots (tuples: T records, the first T1 from pass 1; edges likewise): K2 sorts, K3, K4; leaves the finished graph
 // in the handle.  The reference's count lines are additive over k-mers, so a handle that owns only a k-mer range of the
 // graph reports its share of each line.
 int build_stage(pag_graph *g, uint32_t eps, const Extracted &x, pag_build_stats *st_out, hipEvent_t *ev /*[4]: sort begin, sort end, cluster end, edges end*/) {
     hipStream_t s = g->stream;
     const uint64_t T = x.T, E = x.E, T1 = x.T1, E1 = x.E1;
     int rc;
-    DevBuf b_tk0(g, 30), b_tv0(g, 31), b_tk1(g, 32), b_tv1(g, 33), b_ek0(g, 34), b_ev0(g, 35), b_ek1(g, 36), b_ev1(g, 37);
-    // (the first buffers were filled by the caller; alloc() only hands their pointers back)
-    if ((rc = b_tk0.alloc((T + 1) * 4)) || (rc = b_tv0.alloc((T + 1) * 8)) || (rc = b_ek0.alloc((E + 1) * 4)) || (rc = b_ev0.alloc((E + 1) * 8))) return rc;
-    // the second value buffer of each stream doubles as u64[n] + u32[n] scratch for long segments
-    if ((rc = b_tk1.alloc((T + 1) * 4))) return rc;
-    if ((rc = b_tv1.alloc((T + 1) * 12))) return rc;
-    if ((rc = b_ek1.alloc((E + 1) * 4))) return rc;
-    if ((rc = b_ev1.alloc((E + 1) * 12))) return rc;
-    PAG_HIP_TRY(hipEventRecord(ev[0], s));
+    StreamBufs sb(g);
+    if ((rc = sb.alloc(T, E))) return rc;
+    PAG_HIP_TRY(hipEventRecord(ev[0], s));  // (the sort scratch is allocated by now: a cold handle's ms_sort no longer holds that hipMalloc)
 
     // ---- K2 sorts.  (Measured in round 4 and not kept: the edge stream's sort on a stream and a host thread of its own, so that
     // its histogram / scan launches run beside the other stream's scatter pass — the sort stage took the same 24.6 ms, two
     // persistent scatter kernels never share a CU, and the step was 30 ms slower.)
-    DevBuf b_sorttmp(g, 38);
-    if ((rc = b_sorttmp.alloc(sort_tmp_bytes(std::max(T, E))))) return rc;
     int t_in0 = 1, e_in0 = 1, passes = 0;
     float ms_scatter_t = 0.f, ms_scatter_e = 0.f;
-    if ((rc = sort_pairs(b_tk0.as<uint32_t>(), b_tv0.as<uint64_t>(), b_tk1.as<uint32_t>(), b_tv1.as<uint64_t>(), T,
-                         2 * (int)g->k, b_sorttmp.p, &t_in0, s, &ms_scatter_t, &passes)))
+    if ((rc = sort_pairs(sb.tk0.as<uint32_t>(), sb.tv0.as<uint64_t>(), sb.tk1.as<uint32_t>(), sb.tv1.as<uint64_t>(), T,
+                         2 * (int)g->k, sb.sorttmp.p, &t_in0, s, &ms_scatter_t, &passes)))
         return rc;
-    if ((rc = sort_pairs(b_ek0.as<uint32_t>(), b_ev0.as<uint64_t>(), b_ek1.as<uint32_t>(), b_ev1.as<uint64_t>(), E,
-                         2 * (int)g->k, b_sorttmp.p, &e_in0, s, &ms_scatter_e, nullptr)))
+    if ((rc = sort_pairs(sb.ek0.as<uint32_t>(), sb.ev0.as<uint64_t>(), sb.ek1.as<uint32_t>(), sb.ev1.as<uint64_t>(), E,
+                         2 * (int)g->k, sb.sorttmp.p, &e_in0, s, &ms_scatter_e, nullptr)))
         return rc;
     PAG_HIP_TRY(hipEventRecord(ev[1], s));
     // make the sorted data live in the (k0, v0)-sized buffers, the spare (v1: 12 B/record) is scratch
-    DevBuf *tk = t_in0 ? &b_tk0 : &b_tk1, *tv = t_in0 ? &b_tv0 : &b_tv1;
-    DevBuf *ek = e_in0 ? &b_ek0 : &b_ek1, *evb = e_in0 ? &b_ev0 : &b_ev1;
-    DevBuf b_tscr(g, 43), b_escr(g, 44);
+    DevBuf *tk = t_in0 ? &sb.tk0 : &sb.tk1, *tv = t_in0 ? &sb.tv0 : &sb.tv1;
+    DevBuf *ek = e_in0 ? &sb.ek0 : &sb.ek1, *evb = e_in0 ? &sb.ev0 : &sb.ev1;
+    DevBuf b_tscr(g, ps::T_SCR), b_escr(g, ps::E_SCR);
     uint64_t *t_scratch, *e_scratch;
     if (t_in0) {
-        t_scratch = b_tv1.as<uint64_t>();
+        t_scratch = sb.tv1.as<uint64_t>();
     } else {  // sorted values sit in the big buffer: give the segment kernels a fresh scratch
         if ((rc = b_tscr.alloc((T + 1) * 12))) return rc;
         t_scratch = b_tscr.as<uint64_t>();
     }
     if (e_in0) {
-        e_scratch = b_ev1.as<uint64_t>();
+        e_scratch = sb.ev1.as<uint64_t>();
     } else {
         if ((rc = b_escr.alloc((E + 1) * 12))) return rc;
         e_scratch = b_escr.as<uint64_t>();
     }
 
     // ---- K3 / K4
-    DevBuf b_tseg(g, 45), b_tcnt(g, 46), b_eseg(g, 47), b_long(g, 48), b_lcnt(g, 49), b_ctr(g, 50);
+    DevBuf b_tseg(g, ps::T_SEG), b_tcnt(g, ps::T_CNT), b_eseg(g, ps::E_SEG), b_long(g, ps::SEG_LONG), b_lcnt(g, ps::SEG_LCNT), b_ctr(g, ps::CTR);
     if ((rc = b_tseg.alloc((T + 1) * 4))) return rc;
     if ((rc = b_tcnt.alloc((T + 1) * 2))) return rc;
     if ((rc = b_eseg.alloc((E + 1) * 4))) return rc;
@@ -611,10 +619,11 @@ void keep_debug_streams(pag_graph *g, uint64_t T, uint64_t E) {
     g->dbg_ekey.resize((size_t)E);
     g->dbg_eval.resize((size_t)E);
     hipStreamSynchronize(g->stream);
-    if (T) hipMemcpy(g->dbg_tkey.data(), g->pool[30].p, T * 4, hipMemcpyDeviceToHost);
-    if (T) hipMemcpy(g->dbg_tval.data(), g->pool[31].p, T * 8, hipMemcpyDeviceToHost);
-    if (E) hipMemcpy(g->dbg_ekey.data(), g->pool[34].p, E * 4, hipMemcpyDeviceToHost);
-    if (E) hipMemcpy(g->dbg_eval.data(), g->pool[35].p, E * 8, hipMemcpyDeviceToHost);
+    const StreamPtrs x = streams_at(g, 1, 1);  // (as extract_stage left them)
+    if (T) hipMemcpy(g->dbg_tkey.data(), x.tkey, T * 4, hipMemcpyDeviceToHost);
+    if (T) hipMemcpy(g->dbg_tval.data(), x.tval, T * 8, hipMemcpyDeviceToHost);
+    if (E) hipMemcpy(g->dbg_ekey.data(), x.ekey, E * 4, hipMemcpyDeviceToHost);
+    if (E) hipMemcpy(g->dbg_eval.data(), x.eval, E * 8, hipMemcpyDeviceToHost);
 }
 
 int check_process_args(const pag_graph *g, const pag_build_input *in) {
@@ -749,20 +758,18 @@ int pag_shard_extract_range(pag_graph *g, const pag_build_input *in, uint64_t lo
     }
     // records per (owner, pass), then ONE stable radix pass on the owner bits of the k-mer code
     const int shift = 2 * (int)g->k - lg;
-    DevBuf b_tk0(g, 30), b_tv0(g, 31), b_tk1(g, 32), b_tv1(g, 33), b_ek0(g, 34), b_ev0(g, 35), b_ek1(g, 36), b_ev1(g, 37), b_sorttmp(g, 38), b_ctr(g, 50);
-    if ((rc = b_tk0.alloc((x.T + 1) * 4)) || (rc = b_tv0.alloc((x.T + 1) * 8)) || (rc = b_ek0.alloc((x.E + 1) * 4)) || (rc = b_ev0.alloc((x.E + 1) * 8)) ||
-        (rc = b_tk1.alloc((x.T + 1) * 4)) || (rc = b_tv1.alloc((x.T + 1) * 12)) || (rc = b_ek1.alloc((x.E + 1) * 4)) || (rc = b_ev1.alloc((x.E + 1) * 12)) ||
-        (rc = b_sorttmp.alloc(sort_tmp_bytes(std::max(x.T, x.E)))) || (rc = b_ctr.alloc(512)))
-        return rc;
+    StreamBufs sb(g);
+    DevBuf b_ctr(g, ps::CTR);
+    if ((rc = sb.alloc(x.T, x.E)) || (rc = b_ctr.alloc(512))) return rc;
     unsigned long long *ctr = b_ctr.as<unsigned long long>();
     PAG_HIP_TRY(hipMemsetAsync(ctr, 0, 256, s));
-    if (x.T) owner_counts<<<dim3(1024), dim3(256), 0, s>>>(b_tk0.as<uint32_t>(), x.T, x.T1, shift, ctr);
-    if (x.E) owner_counts<<<dim3(1024), dim3(256), 0, s>>>(b_ek0.as<uint32_t>(), x.E, x.E1, shift, ctr + 16);
+    if (x.T) owner_counts<<<dim3(1024), dim3(256), 0, s>>>(sb.tk0.as<uint32_t>(), x.T, x.T1, shift, ctr);
+    if (x.E) owner_counts<<<dim3(1024), dim3(256), 0, s>>>(sb.ek0.as<uint32_t>(), x.E, x.E1, shift, ctr + 16);
     int t_in0 = 1, e_in0 = 1;
-    if ((rc = sort_pairs(b_tk0.as<uint32_t>(), b_tv0.as<uint64_t>(), b_tk1.as<uint32_t>(), b_tv1.as<uint64_t>(), x.T, lg, b_sorttmp.p, &t_in0, s, nullptr,
+    if ((rc = sort_pairs(sb.tk0.as<uint32_t>(), sb.tv0.as<uint64_t>(), sb.tk1.as<uint32_t>(), sb.tv1.as<uint64_t>(), x.T, lg, sb.sorttmp.p, &t_in0, s, nullptr,
                          nullptr, shift)))
         return rc;
-    if ((rc = sort_pairs(b_ek0.as<uint32_t>(), b_ev0.as<uint64_t>(), b_ek1.as<uint32_t>(), b_ev1.as<uint64_t>(), x.E, lg, b_sorttmp.p, &e_in0, s, nullptr,
+    if ((rc = sort_pairs(sb.ek0.as<uint32_t>(), sb.ev0.as<uint64_t>(), sb.ek1.as<uint32_t>(), sb.ev1.as<uint64_t>(), x.E, lg, sb.sorttmp.p, &e_in0, s, nullptr,
                          nullptr, shift)))
         return rc;
     unsigned long long h[32];
@@ -784,11 +791,11 @@ int pag_shard_take(pag_graph *g, uint32_t *tkey, uint64_t *tval, uint32_t *ekey,
     PAG_HIP_TRY(hipSetDevice(g->device));
     hipStream_t s = g->stream;
     const uint64_t T = g->shard_x[0], E = g->shard_x[1];
-    const int ts = g->shard_in0[0] ? 30 : 32, es = g->shard_in0[1] ? 34 : 36;
-    if (T) PAG_HIP_TRY(hipMemcpyAsync(tkey, g->pool[ts].p, T * 4, hipMemcpyDeviceToDevice, s));
-    if (T) PAG_HIP_TRY(hipMemcpyAsync(tval, g->pool[ts + 1].p, T * 8, hipMemcpyDeviceToDevice, s));
-    if (E) PAG_HIP_TRY(hipMemcpyAsync(ekey, g->pool[es].p, E * 4, hipMemcpyDeviceToDevice, s));
-    if (E) PAG_HIP_TRY(hipMemcpyAsync(eval, g->pool[es + 1].p, E * 8, hipMemcpyDeviceToDevice, s));
+    const StreamPtrs x = streams_at(g, g->shard_in0[0], g->shard_in0[1]);
+    if (T) PAG_HIP_TRY(hipMemcpyAsync(tkey, x.tkey, T * 4, hipMemcpyDeviceToDevice, s));
+    if (T) PAG_HIP_TRY(hipMemcpyAsync(tval, x.tval, T * 8, hipMemcpyDeviceToDevice, s));
+    if (E) PAG_HIP_TRY(hipMemcpyAsync(ekey, x.ekey, E * 4, hipMemcpyDeviceToDevice, s));
+    if (E) PAG_HIP_TRY(hipMemcpyAsync(eval, x.eval, E * 8, hipMemcpyDeviceToDevice, s));
     PAG_HIP_TRY(hipStreamSynchronize(s));
     return PAG_OK;
 }
@@ -804,11 +811,11 @@ int pag_shard_take_part(pag_graph *g, uint64_t t_off, uint64_t t_n, uint32_t *tk
     }
     PAG_HIP_TRY(hipSetDevice(g->device));
     hipStream_t s = g->stream;
-    const int ts = g->shard_in0[0] ? 30 : 32, es = g->shard_in0[1] ? 34 : 36;
-    if (t_n) PAG_HIP_TRY(hipMemcpyAsync(tkey, (const uint32_t *)g->pool[ts].p + t_off, t_n * 4, hipMemcpyDeviceToDevice, s));
-    if (t_n) PAG_HIP_TRY(hipMemcpyAsync(tval, (const uint64_t *)g->pool[ts + 1].p + t_off, t_n * 8, hipMemcpyDeviceToDevice, s));
-    if (e_n) PAG_HIP_TRY(hipMemcpyAsync(ekey, (const uint32_t *)g->pool[es].p + e_off, e_n * 4, hipMemcpyDeviceToDevice, s));
-    if (e_n) PAG_HIP_TRY(hipMemcpyAsync(eval, (const uint64_t *)g->pool[es + 1].p + e_off, e_n * 8, hipMemcpyDeviceToDevice, s));
+    const StreamPtrs x = streams_at(g, g->shard_in0[0], g->shard_in0[1]);
+    if (t_n) PAG_HIP_TRY(hipMemcpyAsync(tkey, x.tkey + t_off, t_n * 4, hipMemcpyDeviceToDevice, s));
+    if (t_n) PAG_HIP_TRY(hipMemcpyAsync(tval, x.tval + t_off, t_n * 8, hipMemcpyDeviceToDevice, s));
+    if (e_n) PAG_HIP_TRY(hipMemcpyAsync(ekey, x.ekey + e_off, e_n * 4, hipMemcpyDeviceToDevice, s));
+    if (e_n) PAG_HIP_TRY(hipMemcpyAsync(eval, x.eval + e_off, e_n * 8, hipMemcpyDeviceToDevice, s));
     PAG_HIP_TRY(hipStreamSynchronize(s));
     return PAG_OK;
 }
@@ -820,7 +827,7 @@ int pag_shard_build(pag_graph *g, const uint32_t *tkey, const uint64_t *tval, ui
     free_graph_results(g);
     hipStream_t s = g->stream;
     int rc;
-    DevBuf b_tk0(g, 30), b_tv0(g, 31), b_ek0(g, 34), b_ev0(g, 35);
+    DevBuf b_tk0(g, ps::TK0), b_tv0(g, ps::TV0), b_ek0(g, ps::EK0), b_ev0(g, ps::EV0);
     if ((rc = b_tk0.alloc((n_t + 1) * 4)) || (rc = b_tv0.alloc((n_t + 1) * 8)) || (rc = b_ek0.alloc((n_e + 1) * 4)) || (rc = b_ev0.alloc((n_e + 1) * 8))) return rc;
     if (n_t) PAG_HIP_TRY(hipMemcpyAsync(b_tk0.p, tkey, n_t * 4, hipMemcpyDeviceToDevice, s));
     if (n_t) PAG_HIP_TRY(hipMemcpyAsync(b_tv0.p, tval, n_t * 8, hipMemcpyDeviceToDevice, s));
@@ -844,13 +851,7 @@ int pag_shard_export(const pag_graph *g, pag_shard_slice *out) {
     if (!g || !out) return PAG_EINVAL;
     out->n_t = g->n_t;
     out->n_e = g->n_e;
-    out->tkey = g->tkey;
-    out->tval = g->tval;
-    out->tseg = g->tseg;
-    out->tcnt = g->tcnt;
-    out->ekey = g->ekey;
-    out->eval = g->eval;
-    out->eseg = g->eseg;
+    point_at(*out, arrays_of(*g));
     out->stats = g->stats;
     return PAG_OK;
 }
@@ -885,26 +886,19 @@ int pag_shard_import(pag_graph *g, const pag_shard_slice *parts, uint32_t n_part
         T += parts[p].n_t;
         E += parts[p].n_e;
     }
-    // the imported streams live in slots of their own: the parts may be the handle's own slice (slots 30..47)
+    // the imported streams live in slots of their own (ps::IMPORT): the parts may be the handle's own slice
     int rc;
-    DevBuf b_tk(g, 52), b_tv(g, 53), b_ts(g, 54), b_tc(g, 55), b_ek(g, 56), b_ev(g, 57), b_es(g, 58);
-    if ((rc = b_tk.alloc((T + 1) * 4)) || (rc = b_tv.alloc((T + 1) * 8)) || (rc = b_ts.alloc((T + 1) * 4)) || (rc = b_tc.alloc((T + 1) * 2)) ||
-        (rc = b_ek.alloc((E + 1) * 4)) || (rc = b_ev.alloc((E + 1) * 8)) || (rc = b_es.alloc((E + 1) * 4)))
-        return rc;
+    for (int a = 0; a < ps::GRAPH_ARRS; ++a)
+        if ((rc = DevBuf(g, ps::family(ps::IMPORT, a)).alloc(((a < ps::GRAPH_TUPLE_ARRS ? T : E) + 1) * ps::GRAPH_ESZ[a]))) return rc;
+    const GraphArrays imp = arrays_in(g, ps::IMPORT);
     pag_build_stats st{};
     uint64_t at = 0, ae = 0;
     for (uint32_t p = 0; p < n_parts; ++p) {
         const pag_shard_slice &P = parts[p];
-        if (P.n_t) {
-            PAG_HIP_TRY(hipMemcpyAsync(b_tk.as<uint32_t>() + at, P.tkey, P.n_t * 4, hipMemcpyDeviceToDevice, s));
-            PAG_HIP_TRY(hipMemcpyAsync(b_tv.as<uint64_t>() + at, P.tval, P.n_t * 8, hipMemcpyDeviceToDevice, s));
-            PAG_HIP_TRY(hipMemcpyAsync(b_ts.as<uint32_t>() + at, P.tseg, P.n_t * 4, hipMemcpyDeviceToDevice, s));
-            PAG_HIP_TRY(hipMemcpyAsync(b_tc.as<uint16_t>() + at, P.tcnt, P.n_t * 2, hipMemcpyDeviceToDevice, s));
-        }
-        if (P.n_e) {
-            PAG_HIP_TRY(hipMemcpyAsync(b_ek.as<uint32_t>() + ae, P.ekey, P.n_e * 4, hipMemcpyDeviceToDevice, s));
-            PAG_HIP_TRY(hipMemcpyAsync(b_ev.as<uint64_t>() + ae, P.eval, P.n_e * 8, hipMemcpyDeviceToDevice, s));
-            PAG_HIP_TRY(hipMemcpyAsync(b_es.as<uint32_t>() + ae, P.eseg, P.n_e * 4, hipMemcpyDeviceToDevice, s));
+        const GraphArrays from = arrays_of(P);
+        for (int a = 0; a < ps::GRAPH_ARRS; ++a) {
+            const uint64_t n = a < ps::GRAPH_TUPLE_ARRS ? P.n_t : P.n_e, off = a < ps::GRAPH_TUPLE_ARRS ? at : ae;
+            if (n) PAG_HIP_TRY(hipMemcpyAsync((char *)imp.p[a] + off * ps::GRAPH_ESZ[a], from.p[a], n * ps::GRAPH_ESZ[a], hipMemcpyDeviceToDevice, s));
         }
         at += P.n_t;
         ae += P.n_e;
@@ -923,31 +917,19 @@ int pag_shard_import(pag_graph *g, const pag_shard_slice *parts, uint32_t n_part
     free_graph_results(g);
     g->n_t = T;
     g->n_e = E;
-    g->tkey = b_tk.as<uint32_t>();
-    g->tval = b_tv.as<uint64_t>();
-    g->tseg = b_ts.as<uint32_t>();
-    g->tcnt = b_tc.as<uint16_t>();
-    g->ekey = b_ek.as<uint32_t>();
-    g->eval = b_ev.as<uint64_t>();
-    g->eseg = b_es.as<uint32_t>();
+    point_at(*g, imp);
     g->stats = st;
     if (total) *total = st;
     return PAG_OK;
 }
 
-// the graph arrays are already in the import slots (52 .. 58: received there, shard_comm.hip): the handle takes them over
+// the graph arrays are already in the import slots (ps::IMPORT: received there, shard_comm.hip): the handle takes them over
 int pag_shard_adopt(pag_graph *g, uint64_t T, uint64_t E, const pag_build_stats *st) {
     if (!g || !st) return PAG_EINVAL;
     free_graph_results(g);
     g->n_t = T;
     g->n_e = E;
-    g->tkey = (uint32_t *)g->pool[52].p;
-    g->tval = (uint64_t *)g->pool[53].p;
-    g->tseg = (uint32_t *)g->pool[54].p;
-    g->tcnt = (uint16_t *)g->pool[55].p;
-    g->ekey = (uint32_t *)g->pool[56].p;
-    g->eval = (uint64_t *)g->pool[57].p;
-    g->eseg = (uint32_t *)g->pool[58].p;
+    point_at(*g, arrays_in(g, ps::IMPORT));
     g->stats = *st;
     return PAG_OK;
 }

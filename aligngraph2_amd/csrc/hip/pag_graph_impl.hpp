@@ -6,6 +6,7 @@
 
 #include "pag_device.hpp"
 #include "pag_travel.hpp"
+#include "pool_slots.hpp"
 
 struct pag_graph {
     int device = 0;
@@ -28,13 +29,13 @@ struct pag_graph {
     // ping-pong pair holds them
     uint64_t shard_x[2] = {0, 0};
     int shard_in0[2] = {1, 1};
-    // device memory pool: every buffer of the pipeline lives in a named slot that is reused (and only
-    // ever grown) across pag_process calls, so steady-state calls do no hipMalloc/hipFree at all
+    // device memory pool: every buffer of the pipeline lives in a named slot (the registry: pool_slots.hpp) that is reused
+    // (and only ever grown) across pag_process calls, so steady-state calls do no hipMalloc/hipFree at all
     struct Slot {
         void *p = nullptr;
         size_t cap = 0;
     };
-    Slot pool[256];
+    Slot pool[pagdev::ps::COUNT];
     // what the pool cost (PAGRAPH_TIMING reports it per stage: at the sizes of BASELINE configs[2] / [3] a fresh handle's tens of
     // GB are seconds of hipMalloc / hipFree)
     double alloc_ms = 0;
@@ -104,7 +105,7 @@ struct DevBuf {  // a view of one pool slot of the handle (never frees; pag_dest
     pag_graph::Slot *sl = nullptr;
     void *p = nullptr;
     DevBuf() = default;
-    DevBuf(pag_graph *gg, int s) : g(gg), sl(&gg->pool[s]) {}
+    DevBuf(pag_graph *gg, ps::Id s) : g(gg), sl(&gg->pool[s]) {}
     DevBuf(pag_graph *gg, pag_graph::Slot *slot) : g(gg), sl(slot) {}
     int alloc(size_t bytes) {
         if (bytes == 0) bytes = 16;
@@ -139,7 +140,42 @@ struct DevBuf {  // a view of one pool slot of the handle (never frees; pag_dest
 };
 
 
-// slot numbers 0..63 belong to pag_process (pag_api.hip), 64..127 to the traversal, 128..191 to pag_prepare (k_prepare.hip), 192.. to pag_shard_select
-enum { TRAV_SLOT0 = 64 };
+// where the extracted (t_in0 = e_in0 = 1: as extract_stage left them) or partitioned (g->shard_in0: the side of each ping-pong
+// pair the owner partition of pag_shard_extract_range ended on) streams are now
+struct StreamPtrs {
+    const uint32_t *tkey;
+    const uint64_t *tval;
+    const uint32_t *ekey;
+    const uint64_t *eval;
+};
+inline StreamPtrs streams_at(const pag_graph *g, int t_in0, int e_in0) {
+    return StreamPtrs{(const uint32_t *)g->pool[t_in0 ? ps::TK0 : ps::TK1].p, (const uint64_t *)g->pool[t_in0 ? ps::TV0 : ps::TV1].p,
+                      (const uint32_t *)g->pool[e_in0 ? ps::EK0 : ps::EK1].p, (const uint64_t *)g->pool[e_in0 ? ps::EV0 : ps::EV1].p};
+}
+
+// the seven arrays of a graph (the handle's, a pag_shard_slice's) in the order of ps::GraphArr: read out, pointed elsewhere
+struct GraphArrays {
+    void *p[ps::GRAPH_ARRS];
+};
+template <typename G>
+GraphArrays arrays_of(const G &x) {
+    return GraphArrays{{(void *)x.tkey, (void *)x.tval, (void *)x.tseg, (void *)x.tcnt, (void *)x.ekey, (void *)x.eval, (void *)x.eseg}};
+}
+template <typename G>
+void point_at(G &x, const GraphArrays &a) {
+    x.tkey = (decltype(x.tkey))a.p[ps::G_TKEY];
+    x.tval = (decltype(x.tval))a.p[ps::G_TVAL];
+    x.tseg = (decltype(x.tseg))a.p[ps::G_TSEG];
+    x.tcnt = (decltype(x.tcnt))a.p[ps::G_TCNT];
+    x.ekey = (decltype(x.ekey))a.p[ps::G_EKEY];
+    x.eval = (decltype(x.eval))a.p[ps::G_EVAL];
+    x.eseg = (decltype(x.eseg))a.p[ps::G_ESEG];
+}
+// the arrays a family of graph slots (ps::IMPORT, ps::SEL_OUT, ps::SEND) holds now
+inline GraphArrays arrays_in(const pag_graph *g, ps::Id base) {
+    GraphArrays a;
+    for (int i = 0; i < ps::GRAPH_ARRS; ++i) a.p[i] = g->pool[ps::family(base, i)].p;
+    return a;
+}
 
 }  // namespace pagdev

@@ -721,14 +721,13 @@ static int shard_run(pag_graph *g, pag_comm *c, const pag_build_input *in, const
             std::vector<uint64_t> counts(4 * (size_t)W);
             const double te0 = now_s();
             if ((rc = pag_shard_extract_range(g, in, lo, hi, (uint32_t)W, counts.data()))) return rc;
-            const int ts = g->shard_in0[0] ? 30 : 32, es = g->shard_in0[1] ? 34 : 36;
+            const StreamPtrs part = streams_at(g, g->shard_in0[0], g->shard_in0[1]);
             const uint64_t Tc = g->shard_x[0], Ec = g->shard_x[1];
-            const size_t esz[4] = {4, 8, 4, 8};
-            const void *src[4] = {g->pool[ts].p, g->pool[ts + 1].p, g->pool[es].p, g->pool[es + 1].p};
+            const void *src[4] = {part.tkey, part.tval, part.ekey, part.eval};
             for (int a = 0; a < 4; ++a) {
                 const uint64_t n = a < 2 ? Tc : Ec;
-                if (!(cb[ch].send[a] = tmp.get((n + 1) * esz[a]))) return PAG_ENOMEM;
-                if (n) PAG_HIP_TRY(hipMemcpyAsync(cb[ch].send[a], src[a], n * esz[a], hipMemcpyDeviceToDevice, s));
+                if (!(cb[ch].send[a] = tmp.get((n + 1) * ps::STREAM_ESZ[a]))) return PAG_ENOMEM;
+                if (n) PAG_HIP_TRY(hipMemcpyAsync(cb[ch].send[a], src[a], n * ps::STREAM_ESZ[a], hipMemcpyDeviceToDevice, s));
             }
             PAG_HIP_TRY(hipStreamSynchronize(s));
             const double te1 = now_s();
@@ -748,11 +747,11 @@ static int shard_run(pag_graph *g, pag_comm *c, const pag_build_input *in, const
                 arrs[a].sb.resize(W);
                 arrs[a].rb.resize(W);
                 for (int r = 0; r < W; ++r) {
-                    arrs[a].sb[r] = (cnt(ch, me, r, q0) + cnt(ch, me, r, q0 + 1)) * esz[a];
-                    arrs[a].rb[r] = (cnt(ch, r, me, q0) + cnt(ch, r, me, q0 + 1)) * esz[a];
+                    arrs[a].sb[r] = (cnt(ch, me, r, q0) + cnt(ch, me, r, q0 + 1)) * ps::STREAM_ESZ[a];
+                    arrs[a].rb[r] = (cnt(ch, r, me, q0) + cnt(ch, r, me, q0 + 1)) * ps::STREAM_ESZ[a];
                     tot += arrs[a].rb[r];
                 }
-                if (!(cb[ch].recv[a] = tmp.get(tot + esz[a]))) return PAG_ENOMEM;
+                if (!(cb[ch].recv[a] = tmp.get(tot + ps::STREAM_ESZ[a]))) return PAG_ENOMEM;
                 arrs[a].send = cb[ch].send[a];
                 arrs[a].recv = cb[ch].recv[a];
             }
@@ -780,14 +779,13 @@ static int shard_run(pag_graph *g, pag_comm *c, const pag_build_input *in, const
                 tmp.ptrs.erase(it);
             }
         }
-    DevBuf b_lk(g, 208), b_lv(g, 209), b_lek(g, 210), b_lev(g, 211);
+    DevBuf b_lk(g, ps::OWN_TK), b_lv(g, ps::OWN_TV), b_lek(g, ps::OWN_EK), b_lev(g, ps::OWN_EV);
     if ((rc = b_lk.alloc((nT + 1) * 4)) || (rc = b_lv.alloc((nT + 1) * 8)) || (rc = b_lek.alloc((nE + 1) * 4)) || (rc = b_lev.alloc((nE + 1) * 8))) return rc;
     mark(1);
     {
         // [pass 1 from rank 0: chunk 0, chunk 1 ..] .. [pass 1 from rank W-1 ..] [pass 2 from rank 0 ..] ..; a chunk's received array
         // is [from rank 0: pass 1, pass 2][from rank 1: ..]
         void *dst_of[4] = {b_lk.p, b_lv.p, b_lek.p, b_lev.p};
-        const size_t esz[4] = {4, 8, 4, 8};
         for (int a = 0; a < 4; ++a) {
             const int q0 = a < 2 ? 0 : 2;
             std::vector<uint64_t> src_at((size_t)C, 0);  // read position in every chunk's received array
@@ -795,9 +793,9 @@ static int shard_run(pag_graph *g, pag_comm *c, const pag_build_input *in, const
             for (int r = 0; r < W; ++r)
                 for (int ch = 0; ch < C; ++ch) {
                     const uint64_t p1 = cnt(ch, r, me, q0), p2 = cnt(ch, r, me, q0 + 1);
-                    const char *from = (const char *)cb[ch].recv[a] + src_at[(size_t)ch] * esz[a];
-                    if (p1) PAG_HIP_TRY(hipMemcpyAsync((char *)dst_of[a] + d1 * esz[a], from, p1 * esz[a], hipMemcpyDeviceToDevice, s));
-                    if (p2) PAG_HIP_TRY(hipMemcpyAsync((char *)dst_of[a] + d2 * esz[a], from + p1 * esz[a], p2 * esz[a], hipMemcpyDeviceToDevice, s));
+                    const char *from = (const char *)cb[ch].recv[a] + src_at[(size_t)ch] * ps::STREAM_ESZ[a];
+                    if (p1) PAG_HIP_TRY(hipMemcpyAsync((char *)dst_of[a] + d1 * ps::STREAM_ESZ[a], from, p1 * ps::STREAM_ESZ[a], hipMemcpyDeviceToDevice, s));
+                    if (p2) PAG_HIP_TRY(hipMemcpyAsync((char *)dst_of[a] + d2 * ps::STREAM_ESZ[a], from + p1 * ps::STREAM_ESZ[a], p2 * ps::STREAM_ESZ[a], hipMemcpyDeviceToDevice, s));
                     src_at[(size_t)ch] += p1 + p2;
                     d1 += p1;
                     d2 += p2;
@@ -815,26 +813,25 @@ static int shard_run(pag_graph *g, pag_comm *c, const pag_build_input *in, const
     std::vector<pag_shard_slice> sel(W);
     std::vector<uint64_t> my_sizes(2 * (size_t)W), all_sizes(2 * (size_t)W * W);
     // (a selection lives in the handle until the next one: copied behind the previous ones into the send buffers)
-    struct Arr {
-        int esz;
-        int slot;
-    };
-    const Arr arrs[7] = {{4, 212}, {8, 213}, {4, 214}, {2, 215}, {4, 216}, {8, 217}, {4, 218}};  // tkey tval tseg tcnt | ekey eval eseg
-    std::vector<uint64_t> at(7, 0);
+    constexpr int NA = ps::GRAPH_ARRS, NT = ps::GRAPH_TUPLE_ARRS;  // the seven arrays of a graph, the first four per tuple
+    const int *const esz = ps::GRAPH_ESZ;
+    auto send_slot = [](int a) { return ps::family(ps::SEND, a); };  // the send buffers
+    std::vector<uint64_t> at(NA, 0);
     std::vector<pag_build_stats> stats_to(W);
     // the send buffers are sized once for what the selections of all destinations usually add up to — the slice itself plus
     // the landing zones and halos that several ranks take (1.2x at N = 4, measured) — so that the loop below neither
     // allocates nor copies what it has already gathered; a block that needs more grows them as before
-    for (int a = 0; a < 7; ++a) {
-        const uint64_t n_slice = a < 4 ? g->n_t : g->n_e;
-        DevBuf b(g, arrs[a].slot);
-        if ((rc = b.alloc((n_slice + n_slice / 2 + 1024) * arrs[a].esz))) return rc;
+    for (int a = 0; a < NA; ++a) {
+        const uint64_t n_slice = a < NT ? g->n_t : g->n_e;
+        DevBuf b(g, send_slot(a));
+        if ((rc = b.alloc((n_slice + n_slice / 2 + 1024) * esz[a]))) return rc;
     }
     // (PAG_SHARD_PIPELINE=0: all selections first, then seven whole all-to-all(v)s, as until round 5)
     const bool pipeline = env_int("PAG_SHARD_PIPELINE", 1) != 0;
     uint64_t T = 0, E = 0;
     std::vector<pag_build_stats> from_owner(W);  // the statistics of what owner o selected for this rank
-    DevBuf imp[7] = {DevBuf(g, 52), DevBuf(g, 53), DevBuf(g, 54), DevBuf(g, 55), DevBuf(g, 56), DevBuf(g, 57), DevBuf(g, 58)};
+    DevBuf imp[NA];
+    for (int a = 0; a < NA; ++a) imp[a] = DevBuf(g, ps::family(ps::IMPORT, a));
     double t_select = 0, t_rxfer = 0, t_rhidden = 0, t_loop1 = 0;
     const uint64_t sent1 = pag_comm_bytes_sent(c);
     if (pipeline) {
@@ -845,7 +842,7 @@ static int shard_run(pag_graph *g, pag_comm *c, const pag_build_input *in, const
             uint64_t n_t, n_e;
             pag_build_stats st;
         };
-        std::vector<std::vector<void *>> piece((size_t)W, std::vector<void *>(7, nullptr));  // [owner][array]
+        std::vector<std::vector<void *>> piece((size_t)W, std::vector<void *>(NA, nullptr));  // [owner][array]
         std::vector<uint64_t> piece_t(W, 0), piece_e(W, 0);
         DevTemp rtmp;
         Xchg X;
@@ -856,19 +853,19 @@ static int shard_run(pag_graph *g, pag_comm *c, const pag_build_input *in, const
             const int dst = (me + i) % W, src = (me - i + W) % W;
             const double ts0 = now_s();
             if ((rc = pag_shard_select(g, &regions[dst], &sel[dst]))) return rc;
-            const void *from[7] = {sel[dst].tkey, sel[dst].tval, sel[dst].tseg, sel[dst].tcnt, sel[dst].ekey, sel[dst].eval, sel[dst].eseg};
+            const GraphArrays from = arrays_of(sel[dst]);
             std::vector<uint64_t> at0 = at;
-            for (int a = 0; a < 7; ++a) {
-                const uint64_t n = a < 4 ? sel[dst].n_t : sel[dst].n_e;
-                DevBuf b(g, arrs[a].slot);
-                const uint64_t need = (at[a] + n + 1) * arrs[a].esz;
+            for (int a = 0; a < NA; ++a) {
+                const uint64_t n = a < NT ? sel[dst].n_t : sel[dst].n_e;
+                DevBuf b(g, send_slot(a));
+                const uint64_t need = (at[a] + n + 1) * esz[a];
                 if (b.sl->cap < need) {
                     // (grown with the old contents kept; an exchange that still reads the old array is waited for first)
                     if ((rc = xchg_end(X))) return rc;
                     void *np = nullptr;
                     const size_t want = need + need / 2 + 256;
                     PAG_HIP_TRY(hipMalloc(&np, want));
-                    if (b.sl->p && at[a]) PAG_HIP_TRY(hipMemcpy(np, b.sl->p, at[a] * arrs[a].esz, hipMemcpyDeviceToDevice));
+                    if (b.sl->p && at[a]) PAG_HIP_TRY(hipMemcpy(np, b.sl->p, at[a] * esz[a], hipMemcpyDeviceToDevice));
                     if (b.sl->p) {  // (as DevBuf::alloc: nothing is freed under a resident walker grid)
                         if (g->defer_free) g->deferred.push_back(b.sl->p);
                         else hipFree(b.sl->p);
@@ -877,7 +874,7 @@ static int shard_run(pag_graph *g, pag_comm *c, const pag_build_input *in, const
                     b.sl->cap = want;
                     if (piece[(size_t)me][a]) piece[(size_t)me][a] = b.sl->p;  // (this rank's own piece lies at the front of these arrays)
                 }
-                if (n) PAG_HIP_TRY(hipMemcpyAsync((char *)b.sl->p + at[a] * arrs[a].esz, from[a], n * arrs[a].esz, hipMemcpyDeviceToDevice, s));
+                if (n) PAG_HIP_TRY(hipMemcpyAsync((char *)b.sl->p + at[a] * esz[a], from.p[a], n * esz[a], hipMemcpyDeviceToDevice, s));
                 at[a] += n;
             }
             PAG_HIP_TRY(hipStreamSynchronize(s));
@@ -896,18 +893,18 @@ static int shard_run(pag_graph *g, pag_comm *c, const pag_build_input *in, const
             piece_e[(size_t)src] = msg[(size_t)src].n_e;
             from_owner[(size_t)src] = msg[(size_t)src].st;
             if (i == 0) {  // this rank's own selection stays where it is
-                for (int a = 0; a < 7; ++a) piece[(size_t)me][a] = (char *)g->pool[arrs[a].slot].p + at0[a] * arrs[a].esz;
+                for (int a = 0; a < NA; ++a) piece[(size_t)me][a] = (char *)g->pool[send_slot(a)].p + at0[a] * esz[a];
                 continue;
             }
-            std::vector<XchgArr> xa(7);
-            for (int a = 0; a < 7; ++a) {
-                const uint64_t n_out = a < 4 ? sel[dst].n_t : sel[dst].n_e, n_in = a < 4 ? piece_t[(size_t)src] : piece_e[(size_t)src];
-                if (!(piece[(size_t)src][a] = rtmp.get((n_in + 1) * arrs[a].esz))) return PAG_ENOMEM;
+            std::vector<XchgArr> xa(NA);
+            for (int a = 0; a < NA; ++a) {
+                const uint64_t n_out = a < NT ? sel[dst].n_t : sel[dst].n_e, n_in = a < NT ? piece_t[(size_t)src] : piece_e[(size_t)src];
+                if (!(piece[(size_t)src][a] = rtmp.get((n_in + 1) * esz[a]))) return PAG_ENOMEM;
                 xa[a].sb.assign(W, 0);
                 xa[a].rb.assign(W, 0);
-                xa[a].sb[(size_t)dst] = n_out * arrs[a].esz;
-                xa[a].rb[(size_t)src] = n_in * arrs[a].esz;
-                xa[a].send = (const char *)g->pool[arrs[a].slot].p + at0[a] * arrs[a].esz;
+                xa[a].sb[(size_t)dst] = n_out * esz[a];
+                xa[a].rb[(size_t)src] = n_in * esz[a];
+                xa[a].send = (const char *)g->pool[send_slot(a)].p + at0[a] * esz[a];
                 xa[a].recv = piece[(size_t)src][a];
             }
             if ((rc = xchg_begin(c, X, std::move(xa)))) return rc;
@@ -922,12 +919,12 @@ static int shard_run(pag_graph *g, pag_comm *c, const pag_build_input *in, const
             T += piece_t[(size_t)o];
             E += piece_e[(size_t)o];
         }
-        for (int a = 0; a < 7; ++a) {
-            if ((rc = imp[a].alloc(((a < 4 ? T : E) + 1) * arrs[a].esz))) return rc;
+        for (int a = 0; a < NA; ++a) {
+            if ((rc = imp[a].alloc(((a < NT ? T : E) + 1) * esz[a]))) return rc;
             uint64_t off = 0;
             for (int o = 0; o < W; ++o) {  // owner order = ascending k-mer ranges
-                const uint64_t n = a < 4 ? piece_t[(size_t)o] : piece_e[(size_t)o];
-                if (n) PAG_HIP_TRY(hipMemcpyAsync((char *)imp[a].p + off * arrs[a].esz, piece[(size_t)o][a], n * arrs[a].esz, hipMemcpyDeviceToDevice, s));
+                const uint64_t n = a < NT ? piece_t[(size_t)o] : piece_e[(size_t)o];
+                if (n) PAG_HIP_TRY(hipMemcpyAsync((char *)imp[a].p + off * esz[a], piece[(size_t)o][a], n * esz[a], hipMemcpyDeviceToDevice, s));
                 off += n;
             }
         }
@@ -938,17 +935,17 @@ static int shard_run(pag_graph *g, pag_comm *c, const pag_build_input *in, const
         my_sizes[2 * d] = sel[d].n_t;
         my_sizes[2 * d + 1] = sel[d].n_e;
         stats_to[d] = sel[d].stats;
-        const void *src[7] = {sel[d].tkey, sel[d].tval, sel[d].tseg, sel[d].tcnt, sel[d].ekey, sel[d].eval, sel[d].eseg};
-        for (int a = 0; a < 7; ++a) {
-            const uint64_t n = a < 4 ? sel[d].n_t : sel[d].n_e;
-            DevBuf b(g, arrs[a].slot);
+        const GraphArrays src = arrays_of(sel[d]);
+        for (int a = 0; a < NA; ++a) {
+            const uint64_t n = a < NT ? sel[d].n_t : sel[d].n_e;
+            DevBuf b(g, send_slot(a));
             // (grown with the old contents kept: DevBuf::alloc replaces the allocation)
-            const uint64_t need = (at[a] + n + 1) * arrs[a].esz;
+            const uint64_t need = (at[a] + n + 1) * esz[a];
             if (b.sl->cap < need) {
                 void *np = nullptr;
                 const size_t want = need + need / 2 + 256;
                 PAG_HIP_TRY(hipMalloc(&np, want));
-                if (b.sl->p && at[a]) PAG_HIP_TRY(hipMemcpy(np, b.sl->p, at[a] * arrs[a].esz, hipMemcpyDeviceToDevice));
+                if (b.sl->p && at[a]) PAG_HIP_TRY(hipMemcpy(np, b.sl->p, at[a] * esz[a], hipMemcpyDeviceToDevice));
                 if (b.sl->p) {
                     if (g->defer_free) g->deferred.push_back(b.sl->p);
                     else hipFree(b.sl->p);
@@ -956,7 +953,7 @@ static int shard_run(pag_graph *g, pag_comm *c, const pag_build_input *in, const
                 b.sl->p = np;
                 b.sl->cap = want;
             }
-            if (n) PAG_HIP_TRY(hipMemcpyAsync((char *)b.sl->p + at[a] * arrs[a].esz, src[a], n * arrs[a].esz, hipMemcpyDeviceToDevice, s));
+            if (n) PAG_HIP_TRY(hipMemcpyAsync((char *)b.sl->p + at[a] * esz[a], src.p[a], n * esz[a], hipMemcpyDeviceToDevice, s));
             at[a] += n;
         }
         PAG_HIP_TRY(hipStreamSynchronize(s));
@@ -970,16 +967,16 @@ static int shard_run(pag_graph *g, pag_comm *c, const pag_build_input *in, const
         T += size_of(o, me, 0);
         E += size_of(o, me, 1);
     }
-    // received straight into the buffers pag_shard_import fills (slots 52 .. 58): owner order = ascending k-mer ranges
-    for (int a = 0; a < 7; ++a) {
-        const uint64_t n = a < 4 ? T : E;
-        if ((rc = imp[a].alloc((n + 1) * arrs[a].esz))) return rc;
+    // received straight into the buffers pag_shard_import fills (ps::IMPORT): owner order = ascending k-mer ranges
+    for (int a = 0; a < NA; ++a) {
+        const uint64_t n = a < NT ? T : E;
+        if ((rc = imp[a].alloc((n + 1) * esz[a]))) return rc;
         std::vector<uint64_t> sb(W), rb(W);
         for (int r = 0; r < W; ++r) {
-            sb[r] = size_of(me, r, a < 4 ? 0 : 1) * arrs[a].esz;
-            rb[r] = size_of(r, me, a < 4 ? 0 : 1) * arrs[a].esz;
+            sb[r] = size_of(me, r, a < NT ? 0 : 1) * esz[a];
+            rb[r] = size_of(r, me, a < NT ? 0 : 1) * esz[a];
         }
-        if ((rc = pag_comm_all_to_all_v(c, g->pool[arrs[a].slot].p, sb.data(), imp[a].p, rb.data()))) return rc;
+        if ((rc = pag_comm_all_to_all_v(c, g->pool[send_slot(a)].p, sb.data(), imp[a].p, rb.data()))) return rc;
     }
         for (int o = 0; o < W; ++o) from_owner[(size_t)o] = all_stats[(size_t)o * W + me];
     }

@@ -129,9 +129,7 @@ uint64_t pow2_at_least(uint64_t x) {
 
 // The traversal's view of a finished graph: compact CSR with dense ids, vertices renumbered by contig coordinate, and the
 // successor records of every vertex (searchSuccessors + checkPosition for all of them, PABruijnGraph.cpp:143-197) — built
-// once per graph and pair of (deviation, error rate), kept in the handle (g->tg).  Pool slots TRAV_SLOT0 .. + TRAV_GRAPH_SLOTS.
-constexpr int TRAV_GRAPH_SLOTS = 22;  // (+ 2 behind them for a regional graph's incomplete-vertex bitmap, + 2 for the view's scratch)
-constexpr int TRAV_EXTRA_SLOTS = 4;  // (incomplete-vertex bitmap + its scratch, the two of the view)
+// once per graph and pair of (deviation, error rate), kept in the handle (g->tg).  Pool slots ps::TG_* (pool_slots.hpp).
 
 // ---- the view of ONE handle's traversals -----------------------------------------------------------------------------
 // A traversal of contig strand S (PAlgorithm::travelSequence for one (contig, orientation)) only ever examines
@@ -286,8 +284,6 @@ int trav_prepare_graph(pag_graph *g, const uint32_t *ctg_len, uint64_t n_ctgs, c
     hipStream_t s = g->stream;
     const uint32_t k = g->k;
     int rc;
-    int slot = TRAV_SLOT0;
-    auto buf = [&](void) { return DevBuf(g, slot++); };
     if (ms_out) *ms_out = 0;
     if (g->tg_ready && (g->tg_dev != deviation || g->tg_err != errorRate)) g->tg_ready = false;
     if (g->tg_ready && g->view_pruned && !(orient && view_serves(g->view_orient, orient, n_ctgs))) g->tg_ready = false;
@@ -300,9 +296,10 @@ int trav_prepare_graph(pag_graph *g, const uint32_t *ctg_len, uint64_t n_ctgs, c
     const double t_entry = now_ms(), alloc_entry = g->alloc_ms;
     const bool prune = orient && !g->regional && !g->view_off && !cfg.view_whole;
     // ---- compact CSR (once per built graph)
-    DevBuf b_ncode = buf(), b_npos = buf(), b_nedge = buf(), b_vpos = buf(), b_vcnt = buf(), b_vnode = buf(), b_eto = buf(),
-           b_estep = buf(), b_bitmap = buf(), b_rank = buf(), b_ctmp = buf(), b_uold = buf(), b_newid = buf(), b_upos = buf(), b_ucnt = buf(),
-           b_soff = buf(), b_succ = buf(), b_ok0 = buf(), b_ov0 = buf(), b_ok1 = buf(), b_ov1 = buf(), b_otmp = buf();
+    DevBuf b_ncode(g, ps::TG_NCODE), b_npos(g, ps::TG_NPOS), b_nedge(g, ps::TG_NEDGE), b_vpos(g, ps::TG_VPOS), b_vcnt(g, ps::TG_VCNT), b_vnode(g, ps::TG_VNODE),
+        b_eto(g, ps::TG_ETO), b_estep(g, ps::TG_ESTEP), b_bitmap(g, ps::TG_BITMAP), b_rank(g, ps::TG_RANK), b_ctmp(g, ps::TG_CTMP), b_uold(g, ps::TG_UOLD),
+        b_newid(g, ps::TG_NEWID), b_upos(g, ps::TG_UPOS), b_ucnt(g, ps::TG_UCNT), b_soff(g, ps::TG_SOFF), b_succ(g, ps::TG_SUCC), b_ok0(g, ps::TG_OK0),
+        b_ov0(g, ps::TG_OV0), b_ok1(g, ps::TG_OK1), b_ov1(g, ps::TG_OV1), b_otmp(g, ps::TG_OTMP);
     const uint64_t nn = g->stats.n_nodes, np = g->stats.n_pos, ne = g->stats.n_uniq_edges;
     if (np >= 0xFFFFFFF0ull || ne >= 0xFFFFFFF0ull) {
         set_error("pag_travel: more than 2^32 vertices/edges");
@@ -354,7 +351,7 @@ int trav_prepare_graph(pag_graph *g, const uint32_t *ctg_len, uint64_t n_ctgs, c
         if ((rc = b_ctmp.alloc(tb))) return rc;
         ViewRegion vr;
         TravView tv{};
-        DevBuf b_view(g, TRAV_SLOT0 + TRAV_GRAPH_SLOTS + 2), b_viewiv(g, TRAV_SLOT0 + TRAV_GRAPH_SLOTS + 3);
+        DevBuf b_view(g, ps::TG_VIEW), b_viewiv(g, ps::TG_VIEW_IV);
         g->view_pruned = false;
         if (prune) {
             if ((rc = trav_view_region(g, cfg, ctg_len, n_ctgs, orient, ref_len, n_refs, startSplit, b_view, &vr))) return rc;
@@ -404,23 +401,22 @@ int trav_prepare_graph(pag_graph *g, const uint32_t *ctg_len, uint64_t n_ctgs, c
         // sort's (28 bytes per tuple slot, 47 GB for a 90 Mb block at 30x) untouched until its next call; a loan never grows a slot.
         struct Lender {
             pag_graph *g;
-            bool lent[64] = {false};
-            bool take(DevBuf &b, size_t bytes) {  // smallest idle build slot that holds `bytes`; false: none (b keeps its own slot)
-                static const int cand[] = {30, 31, 32, 33, 34, 35, 36, 37, 38, 43, 44};
-                int best = -1;
-                for (int c : cand) {
+            bool lent[ps::COUNT] = {false};
+            bool take(DevBuf &b, size_t bytes) {  // smallest idle slot of ps::LENDABLE that holds `bytes`; false: none (b keeps its own slot)
+                ps::Id best = ps::COUNT;  // (none yet)
+                for (ps::Id c : ps::LENDABLE) {
                     const pag_graph::Slot &sl = g->pool[c];
                     if (lent[c] || !sl.p || sl.cap < bytes) continue;
                     if (sl.p == (void *)g->tkey || sl.p == (void *)g->tval || sl.p == (void *)g->ekey || sl.p == (void *)g->eval) continue;
-                    if (best < 0 || sl.cap < g->pool[best].cap) best = c;
+                    if (best == ps::COUNT || sl.cap < g->pool[best].cap) best = c;
                 }
-                if (best < 0) return false;
+                if (best == ps::COUNT) return false;
                 lent[best] = true;
                 b = DevBuf(g, best);
                 b.p = g->pool[best].p;
                 return true;
             }
-            void give_back() { std::fill(lent, lent + 64, false); }
+            void give_back() { std::fill(lent, lent + ps::COUNT, false); }
         } lender{g};
         const DevBuf own_ok0 = b_ok0, own_ov0 = b_ov0, own_ok1 = b_ok1, own_ov1 = b_ov1, own_otmp = b_otmp;
         auto scratch_pairs = [&](uint64_t n_elems, size_t tmp_bytes) -> int {  // (values first: the larger requests get the larger slots)
@@ -446,7 +442,7 @@ int trav_prepare_graph(pag_graph *g, const uint32_t *ctg_len, uint64_t n_ctgs, c
             // (one rank's region of a sharded build: the bands it was given; this handle's own view: the bands it took)
             const std::vector<uint32_t> &riv = prune ? vr.riv : g->region_ref_iv;
             const std::vector<uint8_t> &ropen = prune ? vr.ropen : g->region_ref_open;
-            DevBuf b_inc(g, TRAV_SLOT0 + TRAV_GRAPH_SLOTS), b_inct(g, TRAV_SLOT0 + TRAV_GRAPH_SLOTS + 1);
+            DevBuf b_inc(g, ps::TG_INC), b_inct(g, ps::TG_INC_TMP);
             const uint32_t n_iv = (uint32_t)(riv.size() / 2);
             if ((rc = b_inc.alloc(((size_t)G.n_pos / 32 + 4) * 4)) || (rc = b_inct.alloc(trav_mark_incomplete_tmp_bytes(n_iv)))) return rc;
             if ((rc = trav_mark_incomplete(G, G.n_zero, riv.data(), ropen.data(), n_iv, (uint32_t)deviation, errorRate, b_inc.as<uint32_t>(), b_inct.p, s)))
@@ -506,11 +502,6 @@ int trav_prepare_graph(pag_graph *g, const uint32_t *ctg_len, uint64_t n_ctgs, c
         t_compact = now_ms() - t0;
     }
 
-    static_assert(TRAV_GRAPH_SLOTS == 22, "slots of the traversal graph");
-    if (slot != TRAV_SLOT0 + TRAV_GRAPH_SLOTS) {
-        set_error("trav_prepare_graph: slot bookkeeping");
-        return PAG_EFAULT;
-    }
     *G_out = G;
     if (ms_out) *ms_out = t_compact;
     return PAG_OK;

@@ -42,7 +42,6 @@ struct WalkJobs {
     uint64_t deviation = 0;
     double errorRate = 0, startSplit = 0;
     size_t topK = 0;
-    int slot = TRAV_SLOT0;  // pool slots of the handle are handed out in the order of the buf() calls
     void lap(const char *what) {
         if (!timing) return;
         const double t = now_ms();
@@ -55,7 +54,6 @@ struct WalkJobs {
         laps.emplace_back(what, t - lap_t);
         lap_t = t;
     }
-    DevBuf buf() { return DevBuf(g, slot++); }
     // pinned host staging area (grown, kept in the handle): packed job results on their way in, uploads on their way out
     std::vector<void *> pinned_parked;  // (freeing host memory synchronises the device: never while the walker grid is resident)
     void *pinned(size_t bytes) {
@@ -107,7 +105,7 @@ struct WalkJobs {
     uint32_t n_ctgs = 0, n_sel = 0;
     std::vector<CtgState> st;  // one entry per (contig, orientation) that is walked
     uint64_t nodes_total = 0;
-    DevBuf b_packed, b_nodes, b_starts, b_sizes, b_tc, b_seedout, b_req, b_gset, b_gather, b_vids, b_gbits, b_ckreq, b_ckout;
+    DevBuf b_packed, b_nodes, b_starts, b_sizes, b_tc, b_seedout, b_req, b_gset, b_gather, b_vids, b_gbits, b_ckreq, b_ckout;  // pool slots ps::WALK_* (setup_contigs)
     std::vector<TravContig> tc;
     static constexpr uint32_t SEED_STRIDE = 4096;
     void fill_contigs() {

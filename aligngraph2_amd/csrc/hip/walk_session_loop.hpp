@@ -835,7 +835,7 @@ struct WalkSession : WalkRounds {
                 }
                 at += cs.travel.size();
             }
-            DevBuf b_fin = buf();
+            DevBuf b_fin(g, ps::WALK_FIN);
             if ((rc = b_fin.alloc(tot * 8 + 64)) || (rc = b_gather.alloc(tot * sizeof(pag_path_node) + 64))) return fail(rc);
             if (tot) {
                 PAG_HIP_TRY(hipMemcpyAsync(b_fin.p, hp, tot * 8, hipMemcpyHostToDevice, s));

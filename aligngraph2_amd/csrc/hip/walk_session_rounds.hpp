@@ -524,7 +524,6 @@ struct WalkRounds : WalkJobs {
         topK = std::min<uint32_t>(prm->ref_threads, 8u);
         int rc;
         if ((rc = trav_prepare_graph(g, ctgs->len, ctgs->n_seqs, ref_len, n_refs, deviation, errorRate, &G, &t_compact, orient, startSplit))) return rc;
-        slot += TRAV_GRAPH_SLOTS + TRAV_EXTRA_SLOTS;
         lap("compact");
         return PAG_OK;
     }
@@ -563,8 +562,10 @@ struct WalkRounds : WalkJobs {
         n_sel = (uint32_t)st.size();
         if (n_sel == 0) return PAG_OK;
 
-        b_packed = buf(), b_nodes = buf(), b_starts = buf(), b_sizes = buf(), b_tc = buf(), b_seedout = buf(), b_req = buf();
-        b_gset = buf(), b_gather = buf(), b_vids = buf(), b_gbits = buf();
+        b_packed = DevBuf(g, ps::WALK_PACKED), b_nodes = DevBuf(g, ps::WALK_NODES), b_starts = DevBuf(g, ps::WALK_STARTS), b_sizes = DevBuf(g, ps::WALK_SIZES);
+        b_tc = DevBuf(g, ps::WALK_TC), b_seedout = DevBuf(g, ps::WALK_SEEDOUT), b_req = DevBuf(g, ps::WALK_REQ), b_gset = DevBuf(g, ps::WALK_GSET);
+        b_gather = DevBuf(g, ps::WALK_GATHER), b_vids = DevBuf(g, ps::WALK_VIDS), b_gbits = DevBuf(g, ps::WALK_GBITS);
+        b_ckreq = DevBuf(g, ps::WALK_CKREQ), b_ckout = DevBuf(g, ps::WALK_CKOUT);
         if ((rc = b_packed.alloc(ctgs->packed_bytes + 64)) || (rc = b_nodes.alloc((nodes_total + 1) * 4)) ||
             (rc = b_starts.alloc(mapper.starts.size() * 8 + 8)) || (rc = b_sizes.alloc(mapper.sizes.size() * 8 + 8)) ||
             (rc = b_tc.alloc(n_sel * sizeof(TravContig))))
@@ -580,7 +581,7 @@ struct WalkRounds : WalkJobs {
                 cj.push_back(TravCtgNodesJob{ctgs->byte_off[cs.ci], cs.nodesOff, (uint32_t)cs.len, cs.forward ? 1 : 0});
                 max_len = std::max<uint32_t>(max_len, (uint32_t)cs.len);
             }
-            DevBuf b_cj = buf();
+            DevBuf b_cj(g, ps::WALK_CJ);
             if ((rc = b_cj.alloc(cj.size() * sizeof(TravCtgNodesJob)))) return rc;
             PAG_HIP_TRY(hipMemcpyAsync(b_cj.p, cj.data(), cj.size() * sizeof(TravCtgNodesJob), hipMemcpyHostToDevice, s));
             PAG_HIP_TRY(hipStreamSynchronize(s));  // (cj is a local)
@@ -690,7 +691,6 @@ struct WalkRounds : WalkJobs {
         use_leap_pieces = cfg.leap_pieces;
         deferred.clear();
         deferred.resize(n_sel);
-        b_ckreq = buf(), b_ckout = buf();
         lap("rings");
         return PAG_OK;
     }

@@ -158,10 +158,25 @@ def _prepared_view(lib, g, inp: LoadedInput):
     return out
 
 
+def _hip_runtime():
+    import torch
+    return C.CDLL(os.path.join(os.path.dirname(torch.__file__), "lib", "libamdhip64.so"))
+
+
+def free_device_bytes():
+    """free device memory as hipMemGetInfo reports it (torch's HIP runtime; no torch allocation is made)"""
+    rt = _hip_runtime()
+    rt.hipMemGetInfo.argtypes = [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    free, total = C.c_size_t(), C.c_size_t()
+    rc = rt.hipMemGetInfo(C.byref(free), C.byref(total))
+    if rc != 0:
+        raise RuntimeError(f"hipMemGetInfo failed ({rc})")
+    return free.value
+
+
 def device_bytes(ptr, n):
     """n bytes of device memory as a numpy array (through torch's HIP runtime)"""
-    import torch
-    rt = C.CDLL(os.path.join(os.path.dirname(torch.__file__), "lib", "libamdhip64.so"))
+    rt = _hip_runtime()
     rt.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
     buf = np.empty(n, dtype=np.uint8)
     if n:
@@ -262,11 +277,18 @@ def run_hip(inp: LoadedInput, streams: bool = False, device: int = 0, prepare: b
     keep_streams(streams)
     g = hip_create(inp, device, solid_codes, solid_bitmap)
     try:
-        res = _run(lib, "pag", g, inp, streams, _prepared_view(lib, g, inp) if prepare else None)
+        res = run_on(g, inp, streams, prepare)
         res["n_solid"] = lib.pag_solid_count(g)
         return res
     finally:
         lib.pag_destroy(g)
+
+
+def run_on(g, inp: LoadedInput, streams: bool = False, prepare: bool = True):
+    """run_hip's pag_prepare -> pag_process and export on a handle the caller made (hip_create) and keeps"""
+    lib = hip_lib()
+    keep_streams(streams)
+    return _run(lib, "pag", g, inp, streams, _prepared_view(lib, g, inp) if prepare else None)
 
 
 def first_diff(a: np.ndarray, b: np.ndarray):
