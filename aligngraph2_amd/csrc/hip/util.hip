@@ -292,3 +292,60 @@ int launch_cov_filter(const pag_aln *aln, uint64_t n_aln, const pag_ref *refs_de
 }
 
 }  // namespace pagdev
+
+// test hook: the coverage filter alone on caller-supplied records and reference table (host arrays in, ok[n_aln] out) — scratch
+// sized by cov_tmp_bytes, launch_cov_filter as pag_process runs it (tests/test_gpu_cov_filter.py compares it with the plain
+// definition: coverage per base, sorted, max over the interval).  Precondition, checked here because the difference array of a
+// reference has len + 1 slots: every record with a known target has target < n_refs and t_begin <= t_end <= len.  The device
+// copy of `ok` carries 64 guard bytes behind ok[n_aln]; a changed one is reported as PAG_EFAULT.
+extern "C" int pag_debug_cov_filter(const pag_aln *aln, uint64_t n_aln, const pag_ref *refs, uint64_t n_refs, uint32_t cov_filter,
+                                    uint8_t *ok, int device) {
+    using namespace pagdev;
+    constexpr size_t GUARD = 64;
+    if ((n_aln && (!aln || !ok)) || (n_refs && !refs)) return PAG_EINVAL;
+    for (uint64_t i = 0; i < n_aln; ++i) {
+        if (aln[i].target == PAG_NONE) continue;
+        if (aln[i].target >= n_refs || aln[i].t_begin > aln[i].t_end || aln[i].t_end > refs[aln[i].target].len) {
+            set_error("pag_debug_cov_filter: record %llu outside its reference", (unsigned long long)i);
+            return PAG_EINVAL;
+        }
+    }
+    if (n_aln == 0) return PAG_OK;
+    if (hipSetDevice(device) != hipSuccess) return PAG_ENODEV;
+    const size_t tmp_bytes = cov_tmp_bytes(refs, n_refs);
+    pag_aln *d_aln = nullptr;
+    pag_ref *d_refs = nullptr;
+    uint8_t *d_ok = nullptr;
+    void *d_tmp = nullptr;
+    int rc = PAG_OK;
+    hipError_t e = hipMalloc((void **)&d_aln, n_aln * sizeof(pag_aln));
+    if (e == hipSuccess) e = hipMalloc((void **)&d_refs, (n_refs ? n_refs : 1) * sizeof(pag_ref));
+    if (e == hipSuccess) e = hipMalloc((void **)&d_ok, n_aln + GUARD);
+    if (e == hipSuccess) e = hipMalloc(&d_tmp, tmp_bytes);
+    if (e != hipSuccess) rc = PAG_ENOMEM;
+    if (e == hipSuccess) e = hipMemcpy(d_aln, aln, n_aln * sizeof(pag_aln), hipMemcpyHostToDevice);
+    if (e == hipSuccess && n_refs) e = hipMemcpy(d_refs, refs, n_refs * sizeof(pag_ref), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(d_ok, 0xA5, n_aln + GUARD);
+    if (e == hipSuccess) {
+        rc = launch_cov_filter(d_aln, n_aln, d_refs, refs, n_refs, cov_filter, d_ok, d_tmp, tmp_bytes, nullptr);
+        e = hipDeviceSynchronize();
+    }
+    uint8_t guard[GUARD];
+    if (e == hipSuccess && rc == PAG_OK) e = hipMemcpy(ok, d_ok, n_aln, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rc == PAG_OK) e = hipMemcpy(guard, d_ok + n_aln, GUARD, hipMemcpyDeviceToHost);
+    hipFree(d_aln);
+    hipFree(d_refs);
+    hipFree(d_ok);
+    hipFree(d_tmp);
+    if (rc != PAG_OK) return rc;
+    if (e != hipSuccess) {
+        set_error("pag_debug_cov_filter: %s", hipGetErrorString(e));
+        return PAG_EFAULT;
+    }
+    for (size_t i = 0; i < GUARD; ++i)
+        if (guard[i] != 0xA5) {
+            set_error("pag_debug_cov_filter: byte %zu behind ok[n_aln] was written", i);
+            return PAG_EFAULT;
+        }
+    return PAG_OK;
+}

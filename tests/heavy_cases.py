@@ -23,9 +23,13 @@ def load(name):
 
 
 def materialize(name, dest):
-    """the inputs of a graph-only golden, generated from its spec and checked against the committed hashes"""
+    """the inputs of a graph-only golden, generated from its spec (and rewritten, where the spec names rewrites of
+    tests/prep_cases.py) and checked against the committed hashes"""
     spec, _ = load(name)
     goldens.generate_case(spec, dest)
+    if spec.get("rewrite"):
+        import prep_cases
+        prep_cases.apply_rewrites(dest, spec["rewrite"], spec.get("unlisted_ctg", ""))
     want = json.load(open(os.path.join(GRAPH_ONLY, name, "inputs.sha256")))
     assert sorted(os.listdir(dest)) == sorted(want), f"{name}: input files {sorted(os.listdir(dest))}"
     for f, h in want.items():

@@ -141,6 +141,19 @@ class LoadedInput:
         C.cast(self.view, C.POINTER(PagBuildInput)).contents.outer_sample = outer
         C.cast(self.raw_view, C.POINTER(PagRawInput)).contents.outer_sample = outer
 
+    def set_topk(self, topk_ctg: int, topk_ref: int):
+        """pagraph's readToCtgTopK / readToRefTopK (-1 = all, pagraph.cpp:110-112) replaced in both views"""
+        from aligngraph2_amd.workload import PagBuildInput, PagRawInput
+        for view, typ in ((self.view, PagBuildInput), (self.raw_view, PagRawInput)):
+            v = C.cast(view, C.POINTER(typ)).contents
+            v.topk_ctg, v.topk_ref = topk_ctg, topk_ref
+
+    def set_cov(self, cov: int):
+        """the coverage filter (-v) replaced in both views; the prepared arrays do not depend on it"""
+        from aligngraph2_amd.workload import PagBuildInput, PagRawInput
+        C.cast(self.view, C.POINTER(PagBuildInput)).contents.cov_filter = cov
+        C.cast(self.raw_view, C.POINTER(PagRawInput)).contents.cov_filter = cov
+
     def close(self):
         if self.h:
             self.lib.pagh_free(self.h)

@@ -1,7 +1,15 @@
 """GPU: pag_prepare (the preparation stage on the device, csrc/hip/k_prepare.hip) against the host restatement of the same
 stage (tests/harness/graph_input.cpp — the code the oracle-backed harness runs, pinned with it on the reference's golden
 graph dumps), array for array: per-query lists in std::sort order, filters, flips, n_valid, the contig->reference map with
-its multi-entry bases, both tables, the emission order."""
+its multi-entry bases, both tables, the emission order.
+
+The cases of tests/prep_cases.py (what each one reaches is asserted on the CPU, tests/test_prep_cases.py) bring what the other
+inputs never have: per-read lists of every length 1..19 and longer with ties (the device's insertion sort up to 16 entries, the
+host's std::sort from 17), the coverage-only tail of read_to_ref.aln from both of its causes, records on references and contigs
+that are not the block's (with intervals clamped to a shorter decoy), and a -v that rejects part of pass 2; `reject` also runs
+with a topk on both passes.  Wall time of the slowest of these tests (the `reject` case: three covs on both input paths): not
+measured on an MI355X yet; its oracle side takes 0.5 s on the CPU, and the input is
+120 reads against 8 193 reference bases."""
 import ctypes as C
 import os
 
@@ -11,6 +19,7 @@ import pytest
 import biggen
 import goldens
 import pagctl
+import prep_cases
 import synth
 
 
@@ -163,3 +172,68 @@ def test_prepare_of_the_bench_generator_equals_its_own_digest(k, threads):
         assert st1.n_pos > 100000
     finally:
         lib.pag_destroy(g)
+
+
+# ---- the cases of tests/prep_cases.py ----------------------------------------------------------------------------------------
+_prep_inputs = {}
+
+
+@pytest.fixture(scope="module")
+def prep_inputs(workdir):
+    for name in prep_cases.CASES:
+        d, case = prep_cases.generate(name, str(workdir / ("prep_cases_" + name)))
+        _prep_inputs[name] = (pagctl.LoadedInput(d, threads=case.threads, eps=case.eps, cov=case.cov), case)
+    yield _prep_inputs
+    for inp, _ in _prep_inputs.values():
+        inp.close()
+    _prep_inputs.clear()
+
+
+def _build_both_paths(inp, label):
+    ora = pagctl.run_oracle(inp, streams=True)
+    for prepare in (True, False):
+        pagctl.compare_results(pagctl.run_hip(inp, streams=True, prepare=prepare), ora, label=f"{label} prepare={prepare}")
+    return ora
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(prep_cases.CASES))
+def test_prepare_and_build_on_prep_cases(name, prep_inputs):
+    """pag_prepare against the host restatement, array for array (query_off, the list order under ties, the coverage-only tail of
+    read_to_ref.aln, the clamped t_begin / t_end among them); then the graph from the device-prepared and from the host-prepared
+    input against the oracle's, streams included, at the case's cov — for `reject` also at cov 0 and above every coverage."""
+    inp, case = prep_inputs[name]
+    n1, n2 = _compare(inp, name)
+    assert n1 > 0 and n2 > 0
+    ora = _build_both_paths(inp, f"{name} cov={case.cov}")
+    assert ora["stats"].n_tuples[0] > 0 and ora["stats"].n_tuples[1] > 0
+    if name == "reject":
+        try:
+            inp.set_cov(0)
+            all_of_it = _build_both_paths(inp, f"{name} cov=0")
+            assert all_of_it["stats"].n_tuples[1] > ora["stats"].n_tuples[1]
+            inp.set_cov(100000)
+            none_of_it = _build_both_paths(inp, f"{name} cov=100000")
+            assert none_of_it["stats"].n_tuples[1] == 0 and none_of_it["stats"].n_tuples[0] == ora["stats"].n_tuples[0]
+        finally:
+            inp.set_cov(case.cov)
+
+
+@pytest.mark.gpu
+def test_topk_on_reject_matches_oracle(prep_inputs):
+    """topk_ctg / topk_ref >= 0 on `reject` at its cov: K1's for_active stops after topk alignments, NOT counting those the coverage
+    filter rejects (Aligner.tcc:121-123, 147, 166) — test_prep_cases.py asserts that reads exist for which that matters.  The
+    compiled reference hard-codes -1 for both (pagraph.cpp:110-112); the C oracle, which restates Aligner.tcc:39-41, 98, 121-123,
+    166, is the reference for topk >= 0.  Both input paths."""
+    inp, case = prep_inputs["reject"]
+    seen = set()
+    try:
+        for topk_ctg, topk_ref in ((0, 0), (1, 1), (2, 1), (1, 16), (-1, 3)):
+            inp.set_topk(topk_ctg, topk_ref)
+            ora = _build_both_paths(inp, f"reject topk=({topk_ctg}, {topk_ref})")
+            seen.add(tuple(ora["stats"].n_tuples))
+            if (topk_ctg, topk_ref) == (0, 0):
+                assert tuple(ora["stats"].n_tuples) == (0, 0)
+    finally:
+        inp.set_topk(-1, -1)
+    assert len(seen) == 5, seen  # (every pair changes what is built)

@@ -17,6 +17,34 @@ def _built():
     subprocess.run(["make", "-C", pagctl.ROOT, "harness"], check=True, capture_output=True)
 
 
+def _oracle_dump(ind, out, spec, cov):
+    os.makedirs(out, exist_ok=True)
+    subprocess.run([os.path.join(BIN, "oracle_graph_dump"), "-k", ind + "/kmer.bin", "-c", ind + "/ctg.fasta", "-R", ind + "/ref.fasta",
+                    "-p", ind, "-a", ind + "/aln", "-o", out, "-t", str(spec["threads"]), "--epsilon", str(spec["epsilon"]), "-v",
+                    str(cov)], check=True)
+    assert os.listdir(out) == ["0.graph.txt"]
+    return open(os.path.join(out, "0.graph.txt"), "rb").read()
+
+
+def test_cov_reject_graph_equals_reference_graph(workdir):
+    """tests/prep_cases.py's `reject` at its -v (80): the sorted-coverage filter (quirk Q3) takes a third of pass 2 away, with
+    coverage-only records, records on the decoy references and per-read lists of up to 60 alignments in the input.  The oracle's
+    dump has the length and SHA-256 of the compiled reference's; at -v 0 its count line is the reference's too, and another."""
+    name = "cov_reject_t4"
+    spec, golden = heavy_cases.load(name)
+    assert spec["rewrite"] and spec["cov"] > 0
+    ind = heavy_cases.materialize(name, str(workdir / name / "in"))
+    got = _oracle_dump(ind, str(workdir / name / "graph"), spec, spec["cov"])
+    assert got.split(b"\n", 1)[0] == b"S " + b" ".join(b"%d" % c for c in golden["counts"])
+    assert len(got) == golden["bytes"]
+    assert hashlib.sha256(got).hexdigest() == golden["sha256"]
+    assert got.count(b"\nK ") == golden["n_nodes"]
+    got0 = _oracle_dump(ind, str(workdir / name / "graph0"), spec, 0)
+    assert got0.split(b"\n", 1)[0] == b"S " + b" ".join(b"%d" % c for c in golden["counts_cov0"])
+    # the filter removed something: fewer positions after pass 2 (the fifth number), the same after pass 1 (the second)
+    assert golden["counts"][4] < golden["counts_cov0"][4] and golden["counts"][1] == golden["counts_cov0"][1]
+
+
 def test_count_wrap_graph_equals_reference_graph(workdir):
     """A poly-A k-mer with 151 049 tuples, 85 513 of them left in its counts: the reference's u16 CountType wrapped once.  The oracle's
     dump has the length and SHA-256 of the reference's (byte-identical), and the input still makes a count wrap."""
