@@ -31,14 +31,14 @@ HOST_SRCS := $(wildcard $(HOST_DIR)/*.cpp)
 HOST_LIB_SRCS := $(filter-out %_main.cpp,$(HOST_SRCS))
 HOST_OBJS := $(patsubst $(HOST_DIR)/%.cpp,$(B)/host/%.o,$(HOST_LIB_SRCS))
 HIP_SRCS  := $(wildcard $(HIP_DIR)/*.hip)
-HIP_HDRS  := $(wildcard $(HIP_DIR)/*.h) $(wildcard $(HIP_DIR)/*.hpp) include/pagraph_hip.h
+HIP_HDRS  := $(wildcard $(HIP_DIR)/*.h) $(wildcard $(HIP_DIR)/*.hpp) include/pagraph_hip.h include/pagraph_debug.h
 
 .PHONY: all product harness oracle clean sort_variants
 all: product harness oracle
 
 product: aligngraph2_amd/libpagraph_hip.so aligngraph2_amd/bin/pagraph aligngraph2_amd/bin/kmer_counter aligngraph2_amd/bin/pre_process aligngraph2_amd/bin/pa_cns aligngraph2_amd/bin/paf2aln aligngraph2_amd/libpagraph_host.so
 
-$(B)/host/%.o: $(HOST_DIR)/%.cpp $(wildcard $(HOST_DIR)/*.hpp) include/pagraph_hip.h
+$(B)/host/%.o: $(HOST_DIR)/%.cpp $(wildcard $(HOST_DIR)/*.hpp) include/pagraph_hip.h include/pagraph_debug.h
 	@mkdir -p $(B)/host
 	$(CXX) $(CXXFLAGS) -c $< -o $@
 

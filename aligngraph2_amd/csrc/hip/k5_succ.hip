@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "pag_device.hpp"
+#include "pagraph_debug.h"
 #include "pag_travel.hpp"
 #include "trav_device.hpp"
 

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "pag_graph_impl.hpp"
+#include "pagraph_debug.h"
 #include "walk_config.hpp"
 #include "walk_stitch.hpp"
 #include "walker_grid.hpp"

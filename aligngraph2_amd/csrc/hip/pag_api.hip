@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "pag_device.hpp"
+#include "pagraph_debug.h"
 
 using namespace pagdev;
 

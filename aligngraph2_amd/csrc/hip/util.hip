@@ -14,6 +14,7 @@
 #include <cstdlib>
 
 #include "pag_device.hpp"
+#include "pagraph_debug.h"
 
 namespace pagdev {
 

@@ -18,6 +18,7 @@
 #endif
 
 #include "line_index.hpp"
+#include "pagraph_debug.h"
 
 namespace pagh {
 

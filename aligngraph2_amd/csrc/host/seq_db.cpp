@@ -11,6 +11,7 @@
 #include <stdexcept>
 
 #include "line_index.hpp"
+#include "pagraph_debug.h"
 
 namespace pagh {
 

@@ -170,50 +170,14 @@ def run_config_blocks(pre_dir: str, out_dir: str, argv: Sequence[str], dist=None
 # (18 B per tuple slot + 16 B per edge slot): for BASELINE configs[2] on 4 GPUs (1.08e10 tuples + as many edges) about
 # 49 GB out and 69 GB in per GPU, i.e. ~0.11 s + ~0.15 s at 3 peer links x 153 GB/s if all links are driven at once.
 
-import ctypes as _C
+import ctypes as _C  # noqa: E402
 
-
-class BuildStats(_C.Structure):
-    """pag_build_stats (include/pagraph_hip.h)"""
-    _fields_ = [("merge_edge", _C.c_uint64 * 2), ("total_pos", _C.c_uint64 * 2), ("merge_pos", _C.c_uint64 * 2),
-                ("n_tuples", _C.c_uint64 * 2), ("n_edges", _C.c_uint64 * 2), ("n_nodes", _C.c_uint64),
-                ("n_pos", _C.c_uint64), ("n_uniq_edges", _C.c_uint64), ("ms_extract", _C.c_double),
-                ("ms_sort", _C.c_double), ("ms_cluster", _C.c_double), ("ms_edges", _C.c_double),
-                ("ms_total", _C.c_double), ("ms_sort_kernel", _C.c_double), ("sort_records", _C.c_uint64)]
-
-    def counts(self):
-        return (self.merge_edge[0], self.total_pos[0], self.merge_pos[0], self.merge_edge[1], self.total_pos[1],
-                self.merge_pos[1])
-
-
-class ShardSlice(_C.Structure):
-    """pag_shard_slice (include/pagraph_hip.h)"""
-    _fields_ = [("n_t", _C.c_uint64), ("n_e", _C.c_uint64), ("tkey", _C.c_void_p), ("tval", _C.c_void_p), ("tseg", _C.c_void_p),
-                ("tcnt", _C.c_void_p), ("ekey", _C.c_void_p), ("eval", _C.c_void_p), ("eseg", _C.c_void_p), ("stats", BuildStats)]
-
-
-class Region(_C.Structure):
-    """pag_region (include/pagraph_hip.h)"""
-    _fields_ = [("n_ctg_iv", _C.c_uint64), ("ctg_iv", _C.c_void_p), ("n_ref_iv", _C.c_uint64), ("ref_iv", _C.c_void_p), ("ref_open", _C.c_void_p)]
+from .capi import DTYPES, BuildStats, Region, ShardSlice  # noqa: E402,F401  (pag_path_node, pag_build_stats, pag_region, pag_shard_slice)
 
 
 def bind_shard_api(hip):
-    """ctypes signatures of the pag_shard_* entry points (include/pagraph_hip.h)"""
-    vp, u64 = _C.c_void_p, _C.c_uint64
-    hip.pag_shard_extract.argtypes = [vp, vp, _C.c_uint32, _C.c_uint32, _C.POINTER(u64)]
-    hip.pag_shard_take.argtypes = [vp, vp, vp, vp, vp]
-    hip.pag_shard_take_part.argtypes = [vp, _C.c_uint64, _C.c_uint64, vp, vp, _C.c_uint64, _C.c_uint64, vp, vp]
-    hip.pag_shard_build.argtypes = [vp, vp, vp, u64, u64, vp, vp, u64, u64, _C.c_uint32, _C.POINTER(BuildStats)]
-    hip.pag_shard_export.argtypes = [vp, _C.POINTER(ShardSlice)]
-    hip.pag_shard_take_slice.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
-    hip.pag_shard_import.argtypes = [vp, _C.POINTER(ShardSlice), _C.c_uint32, _C.POINTER(BuildStats)]
-    hip.pag_shard_select.argtypes = [vp, _C.POINTER(Region), _C.POINTER(ShardSlice)]
-    hip.pag_shard_set_region.argtypes = [vp, _C.POINTER(Region)]
-    hip.pag_shard_release_build.argtypes = [vp]
-    for f in ("pag_shard_extract", "pag_shard_take", "pag_shard_take_part", "pag_shard_build", "pag_shard_export", "pag_shard_take_slice", "pag_shard_import",
-              "pag_shard_select", "pag_shard_set_region"):
-        getattr(hip, f).restype = _C.c_int
-    hip.pag_last_error.restype = _C.c_char_p
+    """Nothing left to do: aligngraph2_amd.load_hip() types every entry point, pag_shard_* included (capi.SIGNATURES).  Kept
+    because bench.py calls it before a sharded run."""
 
 
 def mapper_starts(lengths):
@@ -546,13 +510,6 @@ def native_comm(hip, dist, device_ordinal, transport=None):
     rank, world = dist.get_rank(), dist.get_world_size()
     box = [tempfile.mkdtemp(prefix="pagshard_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None) if rank == 0 else None]
     dist.broadcast_object_list(box, src=0)
-    hip.pag_comm_create.restype = _C.c_void_p
-    hip.pag_comm_create.argtypes = [_C.c_int, _C.c_int, _C.c_char_p, _C.c_int, _C.c_char_p, _C.POINTER(_C.c_int)]
-    hip.pag_comm_destroy.argtypes = [_C.c_void_p]
-    hip.pag_comm_bytes_sent.argtypes = [_C.c_void_p]
-    hip.pag_comm_bytes_sent.restype = _C.c_uint64
-    hip.pag_shard_run.argtypes = [_C.c_void_p, _C.c_void_p, _C.c_void_p, _C.c_void_p, _C.POINTER(BuildStats)]
-    hip.pag_shard_run.restype = _C.c_int
     err = _C.c_int()
     c = hip.pag_comm_create(rank, world, box[0].encode(), device_ordinal, transport.encode() if transport else None, _C.byref(err))
     if not c:
@@ -596,9 +553,7 @@ def gather_paths(hip, g, mine, n_ctgs, dist, device):
     import numpy as np
     import torch
     world = dist.get_world_size() if dist else 1
-    REC = 24  # sizeof(pag_path_node)
-    hip.pag_travel_path_oriented.restype = _C.c_void_p
-    hip.pag_travel_path_oriented.argtypes = [_C.c_void_p, _C.c_uint64, _C.c_int, _C.POINTER(_C.c_uint64)]
+    REC = DTYPES["pag_path_node"].itemsize
     meta = np.zeros((2 * n_ctgs,), dtype=np.int64)
     chunks = []
     for slot in sorted(mine):

@@ -33,15 +33,10 @@ import time
 
 import numpy as np
 
-from . import parallel
+from . import capi, parallel
+from .capi import TravelParams, TraverseStats
 
 _NAMES = ("tkey", "tval", "tseg", "tcnt", "ekey", "eval", "eseg")
-
-
-class TravelParams(C.Structure):
-    """pag_travel_params (include/pagraph_hip.h)"""
-    _fields_ = [("ref_threads", C.c_uint32), ("reserved", C.c_uint32), ("deviation", C.c_uint64), ("error_rate", C.c_double),
-                ("start_split", C.c_double), ("min_len", C.c_uint64)]
 
 
 def _used(torch, device):
@@ -78,6 +73,8 @@ def run(hip, host, make_handle, inp, *, n_ranks, eps, k, threads, ctgs, ctg_alns
         halo=200_000, min_len=50, log=None):
     """The block as N ranks, rank after rank, on one device (schedule: module docstring).
 
+    hip / host: the two libraries as the caller opened them (aligngraph2_amd.load_hip() / load_host(), or handles of its own
+    such as bench.load_libs()'s host library, which types only what bench.py calls): the table is applied to both here.
     make_handle() -> a fresh pag_graph* (e.g. pag_create_from_bitmap on the block's solid set); inp: the prepared
     pag_build_input (device resident, owned by the caller); ctgs: [(length)] per contig; ctg_alns / ref_lens: as
     parallel.regions_for takes them, with ref_begin taken from the first alignment of a contig; ctg_seqs / ref_seqs: host
@@ -86,17 +83,8 @@ def run(hip, host, make_handle, inp, *, n_ranks, eps, k, threads, ctgs, ctg_alns
     Returns a dict: count lines, per-rank per-stage device bytes, bytes a rank sends / takes in, held fractions, times, output digest."""
     import torch
     say = log or (lambda *a: None)
-    parallel.bind_shard_api(hip)
-    hip.pag_destroy.argtypes = [C.c_void_p]
-    hip.pag_travel.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-    hip.pag_travel.restype = C.c_int
-    hip.pag_travel_path_oriented.restype = C.c_void_p
-    hip.pag_travel_path_oriented.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
-    hip.pag_csr_sizes.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
-    host.pagh_assemble_paths.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.c_uint32, C.c_uint64, C.c_uint64, C.c_char_p, C.c_char_p, C.c_uint32, C.c_void_p]
-    host.pagh_assemble_paths.restype = C.c_int
-    host.pagh_last_error.restype = C.c_char_p
+    capi.bind(hip)
+    capi.bind(host)
     if os.path.isdir(out_dir) and os.listdir(out_dir):
         raise ValueError(f"rank_serial: {out_dir} exists and is not empty (nothing of the caller's is ever removed)")
     os.makedirs(out_dir, exist_ok=True)
@@ -299,11 +287,6 @@ def run(hip, host, make_handle, inp, *, n_ranks, eps, k, threads, ctgs, ctg_alns
     # ---- rank 0's part: the chains of the whole block from the gathered travel sequences ---------------------------------
     t0 = time.perf_counter()
 
-    class TraverseStats(C.Structure):
-        _fields_ = [("n_contigs", C.c_uint64), ("n_path_nodes", C.c_uint64), ("n_path_bases", C.c_uint64), ("n_chains_emitted", C.c_uint64),
-                    ("n_fasta_bases", C.c_uint64), ("path_checksum", C.c_uint64), ("ms_export", C.c_double), ("ms_traverse", C.c_double),
-                    ("ms_total", C.c_double), ("ms_successors", C.c_double), ("ms_walk", C.c_double), ("walk_rounds", C.c_uint64),
-                    ("walk_jobs", C.c_uint64), ("walk_steps", C.c_uint64), ("walk_classifications", C.c_uint64)]
     ts = TraverseStats()
     orient_arr = np.array(list(orient), dtype=np.int32)
     rc = host.pagh_assemble_paths(None, k, C.byref(ctg_seqs), None, C.byref(ref_seqs), None, orient_arr.ctypes.data, paths, lens, threads, eps, min_len,

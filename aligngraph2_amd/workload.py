@@ -22,48 +22,12 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-PAG_NONE = 0xFFFFFFFF
-ALN_DTYPE = np.dtype([("query", "<u4"), ("target", "<u4"), ("t_begin", "<u4"), ("t_end", "<u4"), ("q_start", "<u4"),
-                      ("t_start", "<u4"), ("n_cols", "<u4"), ("n_valid", "<u4"), ("diff_off", "<u8"), ("flags", "<u4"),
-                      ("reserved", "<u4")])
-CTG_DTYPE = np.dtype([("len", "<u4"), ("selected", "<u4"), ("single_base", "<u4"), ("multi", "<u4"), ("map_off", "<u8")])
-REF_DTYPE = np.dtype([("len", "<u4"), ("accepted", "<u4"), ("single_base", "<u4"), ("reserved", "<u4")])
-FLAG_REV, FLAG_BACK, FLAG_ELIG = 1, 2, 4
-# pag_raw_aln (include/pagraph_hip.h): an ALN record as the parser leaves it, names resolved to indices
-RAW_DTYPE = np.dtype([("query", "<u4"), ("target", "<u4"), ("score", "<u8"), ("q_begin", "<u8"), ("q_end", "<u8"), ("t_begin", "<u8"),
-                      ("t_end", "<u8"), ("diff_off", "<u8"), ("n_cols", "<u4"), ("n_emit", "<u4"), ("n_radv", "<u4"), ("forward", "<u4")])
+from . import capi
+from .capi import PAG_NONE, PagAlnDb, PagBuildInput, PagRawDb, PagRawInput, PagSeqs  # noqa: F401  (bench.py and the tests take them from here)
 
-
-class PagSeqs(C.Structure):
-    _fields_ = [("n_seqs", C.c_uint64), ("byte_off", C.c_void_p), ("len", C.c_void_p), ("packed", C.c_void_p),
-                ("packed_bytes", C.c_uint64)]
-
-
-class PagAlnDb(C.Structure):
-    _fields_ = [("n_aln", C.c_uint64), ("aln", C.c_void_p), ("query_off", C.c_void_p), ("diff", C.c_void_p),
-                ("n_diff_words", C.c_uint64)]
-
-
-class PagBuildInput(C.Structure):
-    _fields_ = [("on_device", C.c_uint32), ("n_threads", C.c_uint32), ("reads", PagSeqs), ("emit_order", C.c_void_p),
-                ("read_to_ctg", PagAlnDb), ("read_to_ref", PagAlnDb), ("n_ctgs", C.c_uint64), ("ctgs", C.c_void_p),
-                ("ctg_ent_off", C.c_void_p), ("n_ctg_ent_off", C.c_uint64), ("ctg_ent", C.c_void_p),
-                ("n_ctg_ent", C.c_uint64), ("n_refs", C.c_uint64), ("refs", C.c_void_p), ("eps", C.c_uint32),
-                ("cov_filter", C.c_uint32), ("outer_sample", C.c_uint32), ("topk_ctg", C.c_int32), ("topk_ref", C.c_int32),
-                ("reserved", C.c_uint32)]
-
-
-class PagRawDb(C.Structure):
-    _fields_ = [("n", C.c_uint64), ("rec", C.c_void_p), ("diff", C.c_void_p), ("n_diff_words", C.c_uint64)]
-
-
-class PagRawInput(C.Structure):
-    _fields_ = [("bulk_on_device", C.c_uint32), ("n_threads", C.c_uint32), ("reads", PagSeqs), ("read_to_ctg", PagRawDb),
-                ("read_to_ref", PagRawDb), ("ctg_to_ref", PagRawDb), ("n_ctgs", C.c_uint64), ("ctg_len", C.c_void_p),
-                ("ctg_selected", C.c_void_p), ("ctg_forward", C.c_void_p), ("n_refs", C.c_uint64), ("ref_len", C.c_void_p),
-                ("ref_accepted", C.c_void_p), ("read_to_ctg_ratio", C.c_double), ("read_to_ref_ratio", C.c_double), ("eps", C.c_uint32),
-                ("cov_filter", C.c_uint32), ("outer_sample", C.c_uint32), ("topk_ctg", C.c_int32), ("topk_ref", C.c_int32),
-                ("reserved", C.c_uint32)]
+# the record arrays the generator fills (include/pagraph_hip.h through capi.py)
+ALN_DTYPE, CTG_DTYPE, REF_DTYPE, RAW_DTYPE = (capi.DTYPES[n] for n in ("pag_aln", "pag_ctg", "pag_ref", "pag_raw_aln"))
+FLAG_REV, FLAG_BACK, FLAG_ELIG = capi.PAG_ALN_REV_STRAND, capi.PAG_ALN_WALK_BACK, capi.PAG_ALN_ELIGIBLE
 
 
 @dataclass

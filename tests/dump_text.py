@@ -9,11 +9,13 @@ import os
 import numpy as np
 
 import goldens
+import pagctl  # noqa: F401  (puts the repository root on sys.path)
 
-PAG_OK, PAG_EINVAL, PAG_ENODEV, PAG_ERANGE = 0, -22, -19, -34
+from aligngraph2_amd import capi
+from aligngraph2_amd.capi import PAG_EINVAL, PAG_ENODEV, PAG_ERANGE, PAG_OK  # noqa: F401  (the tests take them from here)
 
 # pag_path_node (include/pagraph_hip.h)
-NODE = np.dtype([("code", "<u4"), ("ctg", "<u4"), ("ref", "<u4"), ("cnt", "<u2"), ("reserved", "<u2"), ("step", "<i4"), ("vid", "<u4")])
+NODE = capi.DTYPES["pag_path_node"]
 assert NODE.itemsize == 24
 
 M64 = (1 << 64) - 1
@@ -125,13 +127,6 @@ def golden_dumps(name):
 def case_lengths(name, work):
     ind = goldens.materialize_inputs(name, os.path.join(str(work), "dump_in_" + name))
     return fasta_lengths(os.path.join(ind, "ctg.fasta")), fasta_lengths(os.path.join(ind, "ref.fasta"))
-
-
-def bind(lib):
-    lib.pag_render_dump_lines.restype = C.c_int
-    lib.pag_render_dump_lines.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
-                                          C.c_uint64, C.POINTER(C.c_uint64), C.c_int]
-    return lib
 
 
 GUARD = 64

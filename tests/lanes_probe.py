@@ -14,11 +14,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import bench  # noqa: E402
-
-
-class TravelParams(C.Structure):
-    _fields_ = [("ref_threads", C.c_uint32), ("reserved", C.c_uint32), ("deviation", C.c_uint64), ("error_rate", C.c_double),
-                ("start_split", C.c_double), ("min_len", C.c_uint64)]
+from aligngraph2_amd.capi import TravelParams  # noqa: E402
 
 
 def main():
@@ -36,10 +32,6 @@ def main():
     w = biggen.BigWorkload(spec, device="cuda:0")
     torch.cuda.synchronize()
     raw = w.raw_input()
-    hip.pag_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    hip.pag_prepare.restype = C.c_int
-    hip.pag_travel_prepare_for.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-    hip.pag_travel_prepare_for.restype = C.c_int
     ref_np = w.ref.cpu().numpy()
     ctg_seqs, keep1 = bench.host_seqs(w.contig_codes())
     ref_seqs, keep2 = bench.host_seqs([ref_np])

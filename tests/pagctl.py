@@ -22,13 +22,8 @@ REF_DIR = os.path.join(ROOT, "oracle", "_ref")
 import sys  # noqa: E402
 
 sys.path.insert(0, ROOT)
-from aligngraph2_amd.parallel import BuildStats  # noqa: E402,F401  (pag_build_stats, include/pagraph_hip.h)
-
-
-class Csr(C.Structure):
-    _fields_ = [("n_nodes", C.c_uint64), ("n_pos", C.c_uint64), ("n_edges", C.c_uint64),
-                ("node_code", C.c_void_p), ("pos_off", C.c_void_p), ("pos_ctg", C.c_void_p), ("pos_ref", C.c_void_p),
-                ("pos_cnt", C.c_void_p), ("edge_off", C.c_void_p), ("edge_to", C.c_void_p), ("edge_step", C.c_void_p)]
+from aligngraph2_amd import capi  # noqa: E402  (importable without torch)
+from aligngraph2_amd.capi import BuildStats, Csr  # noqa: E402,F401  (pag_build_stats, pag_csr: include/pagraph_hip.h)
 
 
 def ensure_built(targets=("harness", "oracle")):
@@ -38,19 +33,14 @@ def ensure_built(targets=("harness", "oracle")):
         subprocess.run(["make", "-C", ROOT, t], check=True, capture_output=True)
 
 
-def _bind(lib, prefix):
-    vp, u64p = C.c_void_p, C.POINTER(C.c_uint64)
-    getattr(lib, prefix + "_process").argtypes = [vp, vp, C.POINTER(BuildStats)]
-    getattr(lib, prefix + "_process").restype = C.c_int
-    getattr(lib, prefix + "_csr_sizes").argtypes = [vp, u64p, u64p, u64p]
-    getattr(lib, prefix + "_export_csr").argtypes = [vp, C.POINTER(Csr)]
-    getattr(lib, prefix + "_debug_stream_sizes").argtypes = [vp, u64p, u64p]
-    getattr(lib, prefix + "_debug_streams").argtypes = [vp, vp, vp, vp, vp]
-    getattr(lib, prefix + "_reset").argtypes = [vp]
-    getattr(lib, prefix + "_destroy").argtypes = [vp]
-    getattr(lib, prefix + "_destroy").restype = None
-    getattr(lib, prefix + "_solid_count").argtypes = [vp]
-    getattr(lib, prefix + "_solid_count").restype = C.c_uint64
+# the entry points the C oracle restates under its own prefix (oracle/pag_oracle.h): same parameters, same results
+_ORACLE_TWINS = ("process", "csr_sizes", "export_csr", "debug_stream_sizes", "debug_streams", "reset", "destroy", "solid_count")
+
+
+def _bind_twins(lib, prefix):
+    """The prefix_* twins of `lib` get the types of their pag_* originals from capi.SIGNATURES, so the two cannot part."""
+    twins = {"pag_" + t: prefix + "_" + t for t in _ORACLE_TWINS}
+    return capi.bind(lib, rename=twins.get)
 
 
 _libs = {}
@@ -58,14 +48,8 @@ _libs = {}
 
 def hip_lib():
     if "hip" not in _libs:
-        import sys
-        sys.path.insert(0, ROOT)
         import aligngraph2_amd
-        lib = aligngraph2_amd.load_hip()  # (raises if the library is missing: no CPU fallback exists)
-        _bind(lib, "pag")
-        lib.pag_create.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_int)]
-        lib.pag_create.restype = C.c_void_p
-        _libs["hip"] = lib
+        _libs["hip"] = aligngraph2_amd.load_hip()  # (raises if the library is missing: no CPU fallback exists; typed by capi)
     return _libs["hip"]
 
 
@@ -73,7 +57,7 @@ def oracle_lib():
     if "oracle" not in _libs:
         ensure_built(("oracle",))
         lib = C.CDLL(ORACLE_LIB)
-        _bind(lib, "pago")
+        _bind_twins(lib, "pago")
         lib.pago_create.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32]
         lib.pago_create.restype = C.c_void_p
         lib.pago_debug_enable.argtypes = [C.c_void_p, C.c_int]
@@ -82,6 +66,8 @@ def oracle_lib():
         lib.pago_cluster_similar.argtypes = [C.c_uint32] * 4 + [C.c_uint64]
         lib.pago_kmer_codes.argtypes = [C.c_char_p, C.c_uint64, C.c_uint32, C.c_void_p]
         lib.pago_kmer_codes.restype = C.c_uint64
+        lib.pago_debug_max_tile_samples.argtypes = [C.c_void_p]
+        lib.pago_debug_max_tile_samples.restype = C.c_uint64
         _libs["oracle"] = lib
     return _libs["oracle"]
 
@@ -164,7 +150,6 @@ def _prepared_view(lib, g, inp: LoadedInput):
     """pag_prepare: the product's device-side preparation of the block -> a device-resident pag_build_input"""
     import biggen
     out = biggen.PagBuildInput()
-    lib.pag_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     rc = lib.pag_prepare(g, inp.raw_view, C.byref(out))
     if rc != 0:
         raise RuntimeError(f"pag_prepare failed rc={rc} {lib.pag_last_error().decode()}")
@@ -245,8 +230,6 @@ def run_oracle(inp: LoadedInput, streams: bool = False, solid_codes=None):
         res = _run(lib, "pago", g, inp, streams)
         res["n_solid"] = lib.pago_solid_count(g)
         if streams:
-            lib.pago_debug_max_tile_samples.argtypes = [C.c_void_p]
-            lib.pago_debug_max_tile_samples.restype = C.c_uint64
             res["max_tile_samples"] = lib.pago_debug_max_tile_samples(g)
         return res
     finally:
@@ -261,8 +244,6 @@ def hip_create(inp: LoadedInput, device: int = 0, solid_codes=None, solid_bitmap
     if solid_bitmap is not None:
         bits = np.ascontiguousarray(solid_bitmap, dtype=np.uint32)
         n_solid = int(np.unpackbits(bits.view(np.uint8)).sum())
-        lib.pag_create_from_bitmap.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_int)]
-        lib.pag_create_from_bitmap.restype = C.c_void_p
         g = lib.pag_create_from_bitmap(bits.ctypes.data, n_solid, inp.k, 0, device, C.byref(err))
     elif solid_codes is not None:
         codes = np.ascontiguousarray(solid_codes, dtype=np.uint64)

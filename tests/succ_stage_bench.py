@@ -27,14 +27,13 @@ def main():
     import bench
     import pagctl
     from aligngraph2_amd import workload as biggen
+    from aligngraph2_amd.capi import TravelParams
     hip, host = bench.load_libs()
     spec = biggen.BigSpec(seed=args.seed, ref_len=args.ref_len, n_reads=args.reads, read_span=args.read_span, k=14, eps=10, cov=2, threads=16)
     w = biggen.BigWorkload(spec, device="cuda:0")
     torch.cuda.synchronize()
     raw = w.raw_input()
     inp = biggen.PagBuildInput()
-    hip.pag_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    hip.pag_prepare.restype = C.c_int
     err = C.c_int()
     g = hip.pag_create_from_bitmap(w.solid_bits.data_ptr(), w.n_solid, spec.k, 1, 0, C.byref(err))
     assert g, hip.pag_last_error()
@@ -44,13 +43,7 @@ def main():
     orient = np.array([0 if r else 1 for _, _, r in w.ctgs], dtype=np.int32)
     ref_len = np.array([len(w.ref)], dtype=np.uint32)
 
-    class TravelParams(C.Structure):
-        _fields_ = [("ref_threads", C.c_uint32), ("reserved", C.c_uint32), ("deviation", C.c_uint64), ("error_rate", C.c_double),
-                    ("start_split", C.c_double), ("min_len", C.c_uint64)]
     prm = TravelParams(spec.threads, 0, 2 * spec.eps, 0.15, 0.90, 50)
-    hip.pag_travel_prepare_for.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-    hip.pag_travel_prepare_for.restype = C.c_int
-    hip.pag_travel_view_sizes.argtypes = [C.c_void_p] + [C.c_void_p] * 6
     for rep in range(args.reps):
         st = pagctl.BuildStats()
         assert hip.pag_process(g, C.byref(inp), C.byref(st)) == 0, hip.pag_last_error()

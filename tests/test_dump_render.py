@@ -9,6 +9,7 @@ import pytest
 
 import dump_text
 import pagctl
+from aligngraph2_amd import capi
 
 
 def test_restatement_reproduces_every_line_of_every_golden_dump(workdir):
@@ -57,7 +58,7 @@ def test_mapper_restatement_at_its_corners():
 def lib():
     if not os.path.exists(pagctl.HIP_LIB):
         subprocess.run(["make", "-C", pagctl.ROOT, "product"], check=True, capture_output=True)
-    return C.CDLL(pagctl.HIP_LIB)
+    return capi.bind(C.CDLL(pagctl.HIP_LIB))
 
 
 def test_library_exports_the_renderer_and_load_hip_declares_it(lib):
@@ -76,8 +77,6 @@ def test_library_exports_the_renderer_and_load_hip_declares_it(lib):
 def test_renderer_has_no_cpu_fallback(lib):
     """Without a gfx950 device the call fails with PAG_ENODEV (bad arguments are refused before the device is looked for);
     with one it renders."""
-    dump_text.bind(lib)
-    lib.pag_device_available.restype = C.c_int
     recs = dump_text.to_records([(0b0110, 101, 0, 7, 2)])
     ctg_len, ref_len = [100], [100]
     need = C.c_uint64(7)

@@ -14,6 +14,7 @@ import pytest
 
 import goldens
 import pagctl
+from aligngraph2_amd import capi
 
 LENS = np.array([100, 37, 250], dtype=np.uint32)  # the three sequences of func_golden's "mapper" table
 
@@ -21,23 +22,15 @@ LENS = np.array([100, 37, 250], dtype=np.uint32)  # the three sequences of func_
 def _hip_host_only():
     if not os.path.exists(pagctl.HIP_LIB):
         pytest.skip("libpagraph_hip.so not built")
-    lib = C.CDLL(pagctl.HIP_LIB)
-    lib.pag_debug_edit_distance.argtypes = [C.c_char_p, C.c_char_p]
-    lib.pag_debug_edit_distance.restype = C.c_uint64
-    return lib
+    return capi.bind(C.CDLL(pagctl.HIP_LIB))
 
 
 def _bind_mapper(lib, prefix):
-    d2s = getattr(lib, prefix + "_d2s")
-    d2s.argtypes = [C.c_void_p, C.c_uint64, C.c_int64, C.c_int64]
-    d2s.restype = C.c_uint64
-    s2d = getattr(lib, prefix + "_s2d")
-    s2d.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    s2d.restype = None
-    extra = getattr(lib, prefix + "_extra")
-    extra.argtypes = [C.c_void_p, C.c_uint64]
-    extra.restype = C.c_uint64
-    return d2s, s2d, extra
+    """prefix_d2s / _s2d / _extra of `lib`, typed as the library's pag_debug_mapper_* hooks are (capi.SIGNATURES): the harness
+    exports the host mapper under the same three signatures"""
+    names = {"pag_debug_mapper_" + f: prefix + "_" + f for f in ("d2s", "s2d", "extra")}
+    capi.bind(lib, rename=names.get)
+    return tuple(getattr(lib, prefix + "_" + f) for f in ("d2s", "s2d", "extra"))
 
 
 @pytest.mark.parametrize("which", ["host position_mapper.hpp", "hip library Mapper"])

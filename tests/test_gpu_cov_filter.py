@@ -14,7 +14,6 @@ the verdict turns.  Every record keeps the entry's precondition t_begin <= t_end
 Wall time: not measured on an MI355X yet; on the CPU, making a shape's records
 and its numpy verdicts for all F takes under 0.1 s, and a shape has at most 14 727 records and 13 launches of the filter.
 """
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -85,7 +84,6 @@ def test_vectorised_definition_equals_the_loop():
 
 def device_verdicts(aln, refs, F):
     lib = pagctl.hip_lib()
-    lib.pag_debug_cov_filter.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_int]
     ok = np.full(len(aln) + GUARD, 0x5A, np.uint8)
     rc = lib.pag_debug_cov_filter(aln.ctypes.data, len(aln), refs.ctypes.data, len(refs), F, ok.ctypes.data, 0)
     assert rc == 0, lib.pag_last_error()
@@ -138,7 +136,6 @@ def test_cov_filter_entry_rejects_records_outside_their_reference():
     """the entry's precondition (the difference array of a reference has len + 1 slots) is checked on the host, before any launch"""
     refs = np.array([(100, 1, 0, 0)], REF_DTYPE)
     lib = pagctl.hip_lib()
-    lib.pag_debug_cov_filter.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_int]
     for b, e, t in ((0, 101, 0), (60, 50, 0), (0, 10, 1)):
         aln = np.zeros(1, ALN_DTYPE)
         aln["target"], aln["t_begin"], aln["t_end"] = t, b, e

@@ -13,6 +13,7 @@ import pytest
 import dump_text
 import goldens
 import pagctl
+from aligngraph2_amd import capi
 import synth
 
 EXE = os.path.join(pagctl.ROOT, "aligngraph2_amd", "bin", "pagraph")
@@ -22,7 +23,7 @@ I32_MIN, I32_MAX, U32_MAX = -(1 << 31), (1 << 31) - 1, (1 << 32) - 1
 
 @pytest.fixture(scope="module")
 def lib():
-    return dump_text.bind(C.CDLL(pagctl.HIP_LIB))
+    return capi.bind(C.CDLL(pagctl.HIP_LIB))
 
 
 def check(lib, tuples, k, ctg_len, ref_len, label):

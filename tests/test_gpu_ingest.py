@@ -38,14 +38,6 @@ def classify_expect(q: bytes, r: bytes):
     return w, int((cls != 1).sum()), int((cls != 2).sum())
 
 
-def _bind(hip):
-    vp, u64 = C.c_void_p, C.c_uint64
-    hip.pag_pack_text_seqs.argtypes = [vp, C.c_int, u64, vp, vp, u64, vp, vp, u64, C.c_int]
-    hip.pag_pack_text_seqs.restype = C.c_int
-    hip.pag_classify_columns.argtypes = [vp, C.c_int, u64, vp, vp, vp, vp, vp, u64, vp, u64, vp, vp, C.c_int]
-    hip.pag_classify_columns.restype = C.c_int
-
-
 def _pack_on_device(hip, text: bytes, spans, on_device):
     import torch
     off = np.array([a for a, _ in spans], dtype=np.uint64)
@@ -71,7 +63,6 @@ def _pack_on_device(hip, text: bytes, spans, on_device):
 @pytest.mark.parametrize("on_device", [True, False])
 def test_text_sequences_are_packed_like_compressed_seq(on_device):
     hip = pagctl.hip_lib()
-    _bind(hip)
     rng = np.random.default_rng(5)
     alphabet = np.frombuffer(b"ACGTacgtNn-*xRYKM.", dtype=np.uint8)
     seqs = []
@@ -95,7 +86,6 @@ def test_text_sequences_are_packed_like_compressed_seq(on_device):
 def test_alignment_rows_are_classified_like_parse_diff():
     import torch
     hip = pagctl.hip_lib()
-    _bind(hip)
     rng = np.random.default_rng(9)
     alphabet = np.frombuffer(b"ACGT-acgtN", dtype=np.uint8)
     recs = []
@@ -138,7 +128,6 @@ def test_a_golden_block_packs_to_what_the_host_parsers_hand_over(workdir):
     """the reads of a golden block (its FASTQ as text) through pag_pack_text_seqs = the packed array the product's FASTQ parser —
     pinned by the golden outputs — leaves for the same file"""
     hip = pagctl.hip_lib()
-    _bind(hip)
     name = "three_ctg_multi_t4"
     spec = goldens.load_spec(name)
     ind = goldens.materialize_inputs(name, str(workdir / "ingest_in"))

@@ -11,22 +11,14 @@ import pytest
 import kmer_cases
 import pagctl
 import synth
-from biggen import PagSeqs
+from aligngraph2_amd.capi import KmerCountResult, PagSeqs
 from test_kmer_counter_oracle import GOLD, oracle_file_words
 
 EXE = os.path.join(pagctl.ROOT, "aligngraph2_amd", "bin", "kmer_counter")
 
 
-class KmerCountResult(C.Structure):
-    _fields_ = [("min_abundance", C.c_uint64), ("n_solid", C.c_uint64), ("n_kmers_counted", C.c_uint64),
-                ("ms_count", C.c_double), ("ms_select", C.c_double)]
-
-
 def hip_count(rs, on_device, k, threshold, bitmap_ptr, bitmap_on_device):
     lib = pagctl.hip_lib()
-    lib.pag_kmer_count.argtypes = [C.POINTER(PagSeqs), C.c_int, C.c_uint32, C.c_double, C.c_int, C.c_void_p, C.c_int,
-                                   C.POINTER(KmerCountResult)]
-    lib.pag_kmer_count.restype = C.c_int
     res = KmerCountResult()
     rc = lib.pag_kmer_count(C.byref(rs), on_device, k, threshold, 0, bitmap_ptr, bitmap_on_device, C.byref(res))
     assert rc == 0, lib.pag_last_error().decode()

@@ -13,6 +13,7 @@ import pytest
 
 import cns_cases
 import pagctl
+from aligngraph2_amd.capi import CnsAln, CnsPart
 
 EXE = os.path.join(pagctl.ROOT, "aligngraph2_amd", "bin", "pa_cns")
 REF = os.path.join(pagctl.REF_DIR, "pa_cns")
@@ -177,15 +178,6 @@ def test_wave_alignments_that_fill_their_part_and_repeat(tmp_path):
 
 
 # ---- the C ABI: regions too small --------------------------------------------------------------------------------------------
-class CnsAln(C.Structure):
-    _fields_ = [("str_off", C.c_uint64), ("len", C.c_uint32), ("start", C.c_uint32), ("weight", C.c_int32), ("reserved", C.c_uint32)]
-
-
-class CnsPart(C.Structure):
-    _fields_ = [("bb_off", C.c_uint64), ("bb_len", C.c_uint32), ("n_aln", C.c_uint32), ("aln_first", C.c_uint64),
-                ("node_cap", C.c_uint32), ("edge_cap", C.c_uint32), ("aux_cap", C.c_uint32), ("out_cap", C.c_uint32)]
-
-
 def consensus(fn, bb, parts, alns, qpool, tpool):
     n = len(parts)
     P = (CnsPart * n)(*parts)
@@ -204,10 +196,6 @@ def test_wave_reports_the_error_codes_of_the_one_lane_kernel():
     import aligngraph2_amd
     lib = aligngraph2_amd.load_hip()
     fns = [lib.pag_cns_consensus, lib.pag_cns_consensus_wave]
-    for fn in fns:
-        fn.restype = C.c_int
-        fn.argtypes = [C.c_int, C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_char_p, C.c_char_p,
-                       C.c_uint64, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
     rs = np.random.default_rng(24)
     L = 150
     bb = backbone(rs, L)

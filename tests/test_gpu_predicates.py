@@ -26,13 +26,11 @@ def _device(rows, err=0.15, table=False):
     es = np.zeros(n, np.uint8)
     if table:
         through = C.c_uint64()
-        hip.pag_debug_predicates_tab.argtypes = [C.c_void_p, C.c_uint64, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         rc = hip.pag_debug_predicates_tab(rows.ctypes.data, n, err, grade.ctypes.data, es.ctypes.data, 0, C.byref(through))
         assert rc == 0, hip.pag_last_error()
         # every step 1 .. 1023 has a table entry (an interval that could not be pinned down would fall back to the plain path)
         assert through.value == int(((rows[:, 4] > 0) & (rows[:, 4] < 1024)).sum())
         return grade, es
-    hip.pag_debug_predicates.argtypes = [C.c_void_p, C.c_uint64, C.c_double, C.c_void_p, C.c_void_p, C.c_int]
     rc = hip.pag_debug_predicates(rows.ctypes.data, n, err, grade.ctypes.data, es.ctypes.data, 0)
     assert rc == 0, hip.pag_last_error()
     return grade, es

@@ -135,9 +135,6 @@ def test_prepare_of_the_bench_generator_equals_its_own_digest(k, threads):
     w = biggen.BigWorkload(sp, device="cuda:0")
     torch.cuda.synchronize()
     lib = pagctl.hip_lib()
-    lib.pag_create_from_bitmap.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_int)]
-    lib.pag_create_from_bitmap.restype = C.c_void_p
-    lib.pag_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     err = C.c_int()
     g = lib.pag_create_from_bitmap(w.solid_bits.data_ptr(), w.n_solid, sp.k, 1, 0, C.byref(err))
     assert g

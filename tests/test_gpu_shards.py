@@ -14,7 +14,9 @@ import pytest
 import pagctl
 
 sys.path.insert(0, pagctl.ROOT)
+import aligngraph2_amd  # noqa: E402
 from aligngraph2_amd import parallel  # noqa: E402
+from aligngraph2_amd.capi import TravelParams  # noqa: E402
 
 
 def _csr(hip, g):
@@ -28,13 +30,6 @@ def _csr(hip, g):
                                                                                     "edge_off", "edge_to", "edge_step")])
     assert hip.pag_export_csr(C.c_void_p(g), C.byref(csr)) == 0, hip.pag_last_error()
     return (nn.value, npos.value, ne.value), arrs
-
-
-def _bind(hip):
-    hip.pag_create_from_bitmap.restype = C.c_void_p
-    hip.pag_export_csr.argtypes = [C.c_void_p, C.POINTER(pagctl.Csr)]
-    hip.pag_csr_sizes.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
-    parallel.bind_shard_api(hip)
 
 
 def _sharded(hip, w, n_shards, regions=None):
@@ -95,8 +90,7 @@ def test_n_shards_build_the_graph_of_one(n_shards, workdir):
     import torch
     import bench
     import biggen
-    hip, host = bench.load_libs()
-    _bind(hip)
+    hip, host = aligngraph2_amd.load_hip(), aligngraph2_amd.load_host()
     sp = biggen.BigSpec(seed=7, ref_len=1_500_000, n_reads=6000, read_span=4000, k=14, eps=10, ctg_len=300_000, gap_lo=300, gap_hi=3000,
                         rev_ctg_frac=0.3, threads=16, cov=2, solid_min_abundance=2, chunk_reads=512)
     w = biggen.BigWorkload(sp, device="cuda")
@@ -126,19 +120,13 @@ def test_n_shards_build_the_graph_of_one(n_shards, workdir):
     # ... or the contigs are dealt out over the "ranks", each walks its own on its copy of the graph, and the travel
     # sequences are gathered for one chain selection
     n_ctg = len(w.ctgs)
-    hip.pag_travel_path_oriented.restype = C.c_void_p
-    hip.pag_travel_path_oriented.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
     paths = (C.c_void_p * (2 * n_ctg))()
     lens = (C.c_uint64 * (2 * n_ctg))()
     keep = []
 
-    class TravelParams(C.Structure):
-        _fields_ = [("ref_threads", C.c_uint32), ("reserved", C.c_uint32), ("deviation", C.c_uint64), ("error_rate", C.c_double),
-                    ("start_split", C.c_double), ("min_len", C.c_uint64)]
     prm = TravelParams(sp.threads, 0, 2 * sp.eps, 0.15, 0.90, 50)
     ctg_seqs, ref_seqs = seqs[0], seqs[1]
     ref_len = np.array([len(w.ref)], dtype=np.uint32)
-    hip.pag_travel.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     for r, g in enumerate(gs):
         mine = np.array([orient[c] if c % n_shards == r else -1 for c in range(n_ctg)], dtype=np.int32)
         assert hip.pag_travel(g, C.byref(ctg_seqs), mine.ctypes.data, ref_len.ctypes.data, 1, C.byref(prm), None) == 0, hip.pag_last_error()
@@ -155,8 +143,6 @@ def test_n_shards_build_the_graph_of_one(n_shards, workdir):
     out = str(workdir / f"sh{n_shards}_gathered")
     os.makedirs(out, exist_ok=True)
     tsG = bench.TraverseStats()
-    host.pagh_assemble_paths.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.c_uint32, C.c_uint64, C.c_uint64, C.c_char_p, C.c_char_p, C.c_uint32, C.c_void_p]
     rc = host.pagh_assemble_paths(None, sp.k, C.byref(ctg_seqs), None, C.byref(ref_seqs), None, orient.ctypes.data, paths, lens, sp.threads, sp.eps, 50,
                                   out.encode(), b"0_", 0, C.byref(tsG))
     assert rc == 0, host.pagh_last_error()
@@ -175,16 +161,10 @@ def _walk_dealt_and_assemble(hip, host, gs, w, deal, orient, seqs, out):
     import bench
     sp = w.spec
     n_ctg = len(w.ctgs)
-    hip.pag_travel_path_oriented.restype = C.c_void_p
-    hip.pag_travel_path_oriented.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
-    hip.pag_travel.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     paths = (C.c_void_p * (2 * n_ctg))()
     lens = (C.c_uint64 * (2 * n_ctg))()
     keep = []
 
-    class TravelParams(C.Structure):
-        _fields_ = [("ref_threads", C.c_uint32), ("reserved", C.c_uint32), ("deviation", C.c_uint64), ("error_rate", C.c_double),
-                    ("start_split", C.c_double), ("min_len", C.c_uint64)]
     prm = TravelParams(sp.threads, 0, 2 * sp.eps, 0.15, 0.90, 50)
     ctg_seqs, ref_seqs = seqs[0], seqs[1]
     ref_len = np.array([len(w.ref)], dtype=np.uint32)
@@ -205,8 +185,6 @@ def _walk_dealt_and_assemble(hip, host, gs, w, deal, orient, seqs, out):
             lens[slot] = n.value
     os.makedirs(out, exist_ok=True)
     tsG = bench.TraverseStats()
-    host.pagh_assemble_paths.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.c_uint32, C.c_uint64, C.c_uint64, C.c_char_p, C.c_char_p, C.c_uint32, C.c_void_p]
     rc = host.pagh_assemble_paths(None, sp.k, C.byref(ctg_seqs), None, C.byref(ref_seqs), None, orient.ctypes.data, paths, lens, sp.threads, sp.eps, 50,
                                   out.encode(), b"0_", 0, C.byref(tsG))
     assert rc == 0, host.pagh_last_error()
@@ -224,8 +202,7 @@ def test_ranks_hold_their_region_only_and_walk_the_same_paths(n_shards, workdir)
     import torch
     import bench
     import biggen
-    hip, host = bench.load_libs()
-    _bind(hip)
+    hip, host = aligngraph2_amd.load_hip(), aligngraph2_amd.load_host()
     sp = biggen.BigSpec(seed=11, ref_len=3_000_000, n_reads=12000, read_span=4000, k=14, eps=10, ctg_len=250_000, gap_lo=300, gap_hi=3000,
                         rev_ctg_frac=0.3, threads=16, cov=2, solid_min_abundance=2, chunk_reads=512)
     w = biggen.BigWorkload(sp, device="cuda")
@@ -325,10 +302,6 @@ def test_library_communicator_over_rccl_with_itself():
     import tempfile
     import torch
     hip = pagctl.hip_lib()
-    hip.pag_comm_create.restype = C.c_void_p
-    hip.pag_comm_create.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_char_p, C.POINTER(C.c_int)]
-    hip.pag_comm_all_to_all_v.argtypes = [C.c_void_p] * 5
-    hip.pag_comm_destroy.argtypes = [C.c_void_p]
     os.environ["PAG_COMM_FORCE_RCCL"] = "1"
     try:
         d = tempfile.mkdtemp(prefix="pagcomm_")
@@ -386,7 +359,6 @@ def test_rank_serial_run_equals_the_one_gpu_run(n_ranks, workdir):
     import biggen
     from aligngraph2_amd import rank_serial
     hip, host = bench.load_libs()
-    _bind(hip)
     sp = biggen.BigSpec(seed=13, ref_len=3_000_000, n_reads=12000, read_span=4000, k=14, eps=10, ctg_len=250_000, gap_lo=300, gap_hi=3000,
                         rev_ctg_frac=0.3, threads=16, cov=2, solid_min_abundance=2, chunk_reads=512)
     w = biggen.BigWorkload(sp, device="cuda")
@@ -427,11 +399,6 @@ def _comm_worker(rank, world, rdv, q, fail_rank):
     """a rank of a two-process job on the one device ("host" transport): rank `fail_rank` aborts instead of joining the exchange"""
     import torch
     hip = pagctl.hip_lib()
-    hip.pag_comm_create.restype = C.c_void_p
-    hip.pag_comm_create.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_char_p, C.POINTER(C.c_int)]
-    hip.pag_comm_all_to_all_v.argtypes = [C.c_void_p] * 5
-    hip.pag_comm_abort.argtypes = [C.c_void_p, C.c_char_p]
-    hip.pag_comm_destroy.argtypes = [C.c_void_p]
     err = C.c_int()
     c = hip.pag_comm_create(rank, world, rdv.encode(), 0, b"host", C.byref(err))
     if not c:

@@ -25,12 +25,7 @@ import pytest
 
 import goldens
 import pagctl
-from aligngraph2_amd.workload import PagRawInput, PagSeqs
-
-
-class TravelParams(C.Structure):
-    _fields_ = [("ref_threads", C.c_uint32), ("reserved", C.c_uint32), ("deviation", C.c_uint64), ("error_rate", C.c_double),
-                ("start_split", C.c_double), ("min_len", C.c_uint64)]
+from aligngraph2_amd.capi import PagRawInput, PagSeqs, PagSucc, TravelParams
 
 
 def reference_blocks(name):
@@ -174,11 +169,6 @@ def test_every_successor_record_equals_the_reference(name, workdir, monkeypatch)
     ind = goldens.materialize_inputs(name, str(workdir / name / "in"))
     ref_blocks = reference_blocks(name)
     hip = pagctl.hip_lib()
-    hip.pag_travel_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-    hip.pag_travel_prepare_for.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-    hip.pag_debug_succ_sizes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    hip.pag_debug_succ.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    hip.pag_debug_trav_vertices.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     ctg_names = [l[1:].split()[0] for l in open(os.path.join(ind, "ctg.fasta")) if l.startswith(">")]
     totals = {"big_steps": 0, "cut": 0, "markers": 0}
     for block, ref in enumerate(ref_blocks):
@@ -227,10 +217,6 @@ def test_every_successor_record_equals_the_reference(name, workdir, monkeypatch)
         assert totals["cut"] > 0, "the tight view kept every vertex: the cut was not exercised"
 
 
-class PagSucc(C.Structure):
-    _fields_ = [("code", C.c_uint32), ("step", C.c_uint32), ("pos", C.c_uint64), ("grade", C.c_uint32), ("ctg_similar", C.c_uint32)]
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["join_fwd_t1", "succ_corners_t8", "two_blocks_both_orient_t16"])
 def test_pag_successors_answers_like_the_reference_s_successors(name, workdir, monkeypatch):
@@ -243,10 +229,6 @@ def test_pag_successors_answers_like_the_reference_s_successors(name, workdir, m
     ind = goldens.materialize_inputs(name, str(workdir / name / "in_q"))
     ref_blocks = reference_blocks(name)
     hip = pagctl.hip_lib()
-    hip.pag_travel_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-    hip.pag_travel_prepare_for.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-    hip.pag_successors.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_uint64]
-    hip.pag_successors.restype = C.c_int64
     ctg_names = [l[1:].split()[0] for l in open(os.path.join(ind, "ctg.fasta")) if l.startswith(">")]
     for block, ref in enumerate(ref_blocks):
         inp = pagctl.LoadedInput(ind, threads=spec["threads"], eps=spec["epsilon"], cov=spec["cov"], block=block)

@@ -10,11 +10,7 @@ import numpy as np
 import pytest
 
 import pagctl
-
-
-class TravelParams(C.Structure):
-    _fields_ = [("ref_threads", C.c_uint32), ("reserved", C.c_uint32), ("deviation", C.c_uint64), ("error_rate", C.c_double),
-                ("start_split", C.c_double), ("min_len", C.c_uint64)]
+from aligngraph2_amd.capi import TravelParams
 
 
 @pytest.mark.gpu
@@ -29,14 +25,10 @@ def test_successor_records_do_not_depend_on_how_they_are_built(monkeypatch):
     torch.cuda.synchronize()
     inp = w.build_input()
     err = C.c_int()
-    hip.pag_create_from_bitmap.restype = C.c_void_p
     g = C.c_void_p(hip.pag_create_from_bitmap(w.solid_bits.data_ptr(), w.n_solid, sp.k, 1, 0, C.byref(err)))
     ctg_seqs, keep = bench.host_seqs(w.contig_codes())
     ref_len = np.array([len(w.ref)], dtype=np.uint32)
     prm = TravelParams(sp.threads, 0, 2 * sp.eps, 0.15, 0.90, 50)
-    hip.pag_travel_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-    hip.pag_debug_succ_sizes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    hip.pag_debug_succ.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     got = {}
     for mode in ("default", "heavy=4", "heavy=0", "order=8", "order=1", "stream=4096"):
         monkeypatch.delenv("PAG_SUCC_HEAVY", raising=False)

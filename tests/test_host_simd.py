@@ -3,22 +3,14 @@ CompressedSeq's packing, CompressedSeq.cpp:8-38) against their scalar restatemen
 alphabets with gaps, lower case, NULs and the characters one bit away from C / G / T, reference rows shorter and longer than the
 query row."""
 import ctypes as C
-import os
 
 import numpy as np
 
 import aligngraph2_amd
-import pagctl
 
 
 def _host():
-    aligngraph2_amd.load_hip()  # (the host library links the C-ABI library: loaded first, by its path)
-    lib = C.CDLL(os.path.join(pagctl.ROOT, "aligngraph2_amd", "libpagraph_host.so"))
-    lib.pagh_debug_classify_columns.argtypes = [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-    lib.pagh_debug_classify_columns.restype = None
-    lib.pagh_debug_pack_bases.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_int]
-    lib.pagh_debug_pack_bases.restype = None
-    return lib
+    return aligngraph2_amd.load_host()  # (the host library links the C-ABI library: that one is loaded first, by its path)
 
 
 def test_column_classes_wide_equal_scalar():

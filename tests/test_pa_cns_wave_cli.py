@@ -1,7 +1,6 @@
 """CPU: the lane-parallel device backend of bin/pa_cns (PA_CNS_BACKEND=wave, pag_cns_consensus_wave in csrc/hip/k_cns_wave.hip)
 is part of the library's C ABI, and where no gfx950 device is present the executable accepts the backend name and fails with
 the reason: there is no host fallback behind it.  The device runs it in tests/test_gpu_pa_cns_wave.py."""
-import ctypes as C
 import os
 import subprocess
 
@@ -27,7 +26,6 @@ def test_library_exports_the_wave_entry_point():
 
 def test_wave_backend_without_a_device_exits_1_with_the_reason(tmp_path):
     lib = _lib()
-    lib.pag_device_available.restype = C.c_int
     if lib.pag_device_available() != 0:
         pytest.skip("a gfx950 device is present: tests/test_gpu_pa_cns_wave.py runs the backend")
     case = cns_cases.CASES["one_part"]
