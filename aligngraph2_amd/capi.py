@@ -20,11 +20,11 @@ import numpy as np
 
 # ---- constants ------------------------------------------------------------------------------------------------------------
 CONSTANTS = {
-    "PAG_OK": 0, "PAG_EINVAL": -22, "PAG_ENOMEM": -12, "PAG_ENODEV": -19, "PAG_ERANGE": -34, "PAG_EFAULT": -14,
+    "PAG_OK": 0, "PAG_EINVAL": -22, "PAG_ENOMEM": -12, "PAG_ENODEV": -19, "PAG_ERANGE": -34, "PAG_EFAULT": -14, "PAG_EDOM": -33,
     "PAG_NONE": 0xFFFFFFFF,
     "PAG_ALN_REV_STRAND": 1, "PAG_ALN_WALK_BACK": 2, "PAG_ALN_ELIGIBLE": 4,
     "PAG_ORIENT_NONE": -1, "PAG_ORIENT_REVERSE": 0, "PAG_ORIENT_FORWARD": 1, "PAG_ORIENT_BOTH": 2,
-    "PAG_TRAVEL_RENDER_DUMPS": 1,
+    "PAG_TRAVEL_RENDER_DUMPS": 1, "PAG_TRAVEL_RENDER_SEQS": 2,
 }
 globals().update(CONSTANTS)
 
@@ -209,6 +209,9 @@ SIGNATURES = {
     "pag_reserve_walk_arena": (_int, [_vp, _u64]),
     "pag_render_dump_lines": (_int, [_vp, _u64, _u32, _vp, _u64, _vp, _u64, _vp, _u64, _u64p, _int]),
     "pag_travel_dump_text": (_vp, [_vp, _u64, _int, _u64p]),
+    "pag_render_path_sequence": (_int, [_vp, _u64, _u32, _vp, _vp, _u64, _f64, _vp, _u64, _u64p, _int]),
+    "pag_travel_seq_sources": (_int, [_vp, _vp]),
+    "pag_travel_seq_text": (_vp, [_vp, _u64, _int, _u64p]),
     "pag_pack_text_seqs": (_int, [_vp, _int, _u64, _vp, _vp, _u64, _vp, _vp, _u64, _int]),
     "pag_classify_columns": (_int, [_vp, _int, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _int]),
     "pag_classify_columns_host": (_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _int]),
@@ -225,6 +228,8 @@ SIGNATURES = {
     "pagh_assemble_paths": (_int, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u64, _u64, _cs, _cs, _u32, _vp]),
     "pagh_assemble_paths_text": (_int, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u64, _u64, _cs, _cs, _u32,
                                         _vp]),
+    "pagh_assemble_paths_seq": (_int, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u64, _u64, _cs, _cs,
+                                       _u32, _vp]),
     "pagh_release": (None, [_vp]),
     "pagh_last_error": (_cs, []),
     # include/pagraph_debug.h: test hooks, not API

@@ -53,35 +53,6 @@ __device__ __forceinline__ uint32_t digits_u64(uint64_t v) {
 }
 __device__ __forceinline__ uint32_t chars_i64(int64_t v) { return v < 0 ? 1u + digits_u64(0ull - (uint64_t)v) : digits_u64((uint64_t)v); }
 
-// PositionMapper::singleToDual (position_mapper.hpp:33-47): upper_bound over the n + 1 starts, one step back unless at the
-// beginning; the offset is the unsigned 64-bit difference, here a signed one tested for "negative or >= 2 * size" (the same
-// set of values); past the last start the size reads as 0 (the library's own Mapper, trav_prepare_host.hpp).
-template <typename Starts>
-__device__ __forceinline__ void single_to_dual(Starts starts, const uint32_t *__restrict__ sizes, uint32_t n, uint32_t single, int32_t *idx, int64_t *off) {
-    if (single == 0u) {
-        *idx = 0;
-        *off = 0;
-        return;
-    }
-    uint32_t lo = 0, hi = n ? n + 1u : 0u;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (starts[mid] <= single) lo = mid + 1u;
-        else hi = mid;
-    }
-    const uint32_t i = lo ? lo - 1u : 0u;
-    const int64_t start = n ? (int64_t)starts[i] : 0;
-    const int64_t size2 = i < n ? 2 * (int64_t)sizes[i] : 0;
-    int64_t o = (int64_t)single - start;
-    if (o < 0 || o >= size2) {
-        o -= size2;
-        *idx = -(int32_t)(i + 1u);
-    } else {
-        *idx = (int32_t)(i + 1u);
-    }
-    *off = o;
-}
-
 __device__ __forceinline__ uint32_t dump_line_len(const DumpFields &f, uint32_t k) {
     return k + 9u + digits_u32(f.ctg) + digits_u32(f.ref) + digits_u32(f.cnt) + chars_i64(f.step) + chars_i64(f.cidx) + chars_i64(f.coff) + chars_i64(f.ridx) +
            chars_i64(f.roff);

@@ -73,6 +73,20 @@ const char *pag_travel_dump_text(const pag_graph *g, uint64_t ctg_index, int for
     return g->text_ptr[slot];
 }
 
+// ... and its consensus sequence (PAG_TRAVEL_RENDER_SEQS after pag_travel_seq_sources)
+const char *pag_travel_seq_text(const pag_graph *g, uint64_t ctg_index, int forward, uint64_t *bytes) {
+    const uint64_t slot = 2 * ctg_index + (forward ? 0 : 1);
+    if (bytes) *bytes = 0;
+    if (!g || slot >= g->path_valid.size() || !g->path_valid[slot] || slot >= g->seq_ptr.size() || !g->seq_ptr[slot]) return nullptr;
+    if (bytes) *bytes = g->seq_len[slot];
+    return g->seq_ptr[slot];
+}
+int pag_travel_seq_sources(pag_graph *g, const pag_seqs *refs) {
+    if (!g) return PAG_EINVAL;
+    g->seq_refs = refs;  // (NULL: none)
+    return PAG_OK;
+}
+
 const pag_path_node *pag_travel_path(const pag_graph *g, uint64_t ctg_index, uint64_t *len) {
     if (g && 2 * ctg_index + 1 < g->path_valid.size() && !g->path_valid[2 * ctg_index]) return pag_travel_path_oriented(g, ctg_index, 0, len);
     return pag_travel_path_oriented(g, ctg_index, 1, len);
@@ -179,6 +193,7 @@ int pag_travel(pag_graph *g, const pag_seqs *ctgs, const int32_t *orient, const 
         g->view_fallbacks += 1;
         rc = travel_once(g, ctgs, orient, ref_len, n_refs, prm, stats);
     }
+    g->seq_refs = nullptr;  // (the caller's array is not ours beyond this call)
     return rc;
 }
 static int travel_once(pag_graph *g, const pag_seqs *ctgs, const int32_t *orient, const uint32_t *ref_len, uint64_t n_refs,

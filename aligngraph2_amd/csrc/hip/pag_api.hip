@@ -89,6 +89,8 @@ void free_graph_results(pag_graph *g) {  // the memory stays in the pool
     g->path_ptr.clear();
     g->text_ptr.clear();
     g->text_len.clear();
+    g->seq_ptr.clear();
+    g->seq_len.clear();
 }
 
 __global__ void chunk_counts(const pag_aln *__restrict__ aln, uint64_t n, uint32_t *__restrict__ out) {
@@ -689,7 +691,8 @@ extern "C" int pag_reserve_walk_arena(pag_graph *g, uint64_t contig_bases) {
         for (size_t b : g->fetch_chunk_bytes) have += b;
         // (PAGRAPH_DEVICE_DUMPS=1, the switch of the callers that will ask pag_travel for the dump text: its buffers come out of the
         // same chunks, ~0.24 path vertices per contig base at up to ~90 bytes of a line's bound)
-        const size_t per_base = 14 + (env_int("PAGRAPH_DEVICE_DUMPS", 0) == 1 ? 22 : 0);
+        // (PAGRAPH_DEVICE_SEQS=1 likewise: a path's sequence is about as long as its contig)
+        const size_t per_base = 14 + (env_int("PAGRAPH_DEVICE_DUMPS", 0) == 1 ? 22 : 0) + (env_int("PAGRAPH_DEVICE_SEQS", 0) == 1 ? 2 : 0);
         const size_t want_pinned = std::min<size_t>((size_t)contig_bases * per_base, (size_t)4 << 30);
         while (have < want_pinned) {
             void *q = nullptr;

@@ -68,6 +68,11 @@ struct pag_graph {
     // the renderings use: the PositionMapper tables, the scratch of the epilogue's renderings
     std::vector<const char *> text_ptr;
     std::vector<uint64_t> text_len;
+    // ... and their consensus sequences (PAG_TRAVEL_RENDER_SEQS, k5_seq.hip); seq_refs: the references' bases as
+    // pag_travel_seq_sources left them for the next pag_travel
+    std::vector<const char *> seq_ptr;
+    std::vector<uint64_t> seq_len;
+    const pag_seqs *seq_refs = nullptr;
     void *dump_tables = nullptr, *dump_scratch = nullptr;
     size_t dump_tables_cap = 0, dump_scratch_cap = 0;
     // device arena of the walker's job buffers (bump pointer, reset by every pag_travel)

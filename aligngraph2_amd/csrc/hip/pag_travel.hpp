@@ -260,6 +260,36 @@ struct DumpTables {
     const uint32_t *cstart, *csize, *rstart, *rsize;  // [nc + 1] [nc] [nr + 1] [nr]
     uint32_t nc, nr, in_lds;
 };
+#ifdef __HIPCC__
+// PositionMapper::singleToDual (position_mapper.hpp:33-47): upper_bound over the n + 1 starts, one step back unless at the
+// beginning; the offset is the unsigned 64-bit difference, here a signed one tested for "negative or >= 2 * size" (the same
+// set of values); past the last start the size reads as 0 (the library's own Mapper, trav_prepare_host.hpp).
+template <typename Starts>
+__device__ __forceinline__ void single_to_dual(Starts starts, const uint32_t *__restrict__ sizes, uint32_t n, uint32_t single, int32_t *idx, int64_t *off) {
+    if (single == 0u) {
+        *idx = 0;
+        *off = 0;
+        return;
+    }
+    uint32_t lo = 0, hi = n ? n + 1u : 0u;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (starts[mid] <= single) lo = mid + 1u;
+        else hi = mid;
+    }
+    const uint32_t i = lo ? lo - 1u : 0u;
+    const int64_t start = n ? (int64_t)starts[i] : 0;
+    const int64_t size2 = i < n ? 2 * (int64_t)sizes[i] : 0;
+    int64_t o = (int64_t)single - start;
+    if (o < 0 || o >= size2) {
+        o -= size2;
+        *idx = -(int32_t)(i + 1u);
+    } else {
+        *idx = (int32_t)(i + 1u);
+    }
+    *off = o;
+}
+#endif
 // host arrays -> one blob in the layout dump_tables_at() reads (after it was copied to the device); false: out of bounds
 bool dump_tables_build(const uint32_t *ctg_len, uint64_t n_ctgs, const uint32_t *ref_len, uint64_t n_refs, std::vector<uint32_t> &blob);
 DumpTables dump_tables_at(const uint32_t *dev, uint64_t n_ctgs, uint64_t n_refs);
@@ -270,5 +300,30 @@ size_t dump_scratch_bytes(uint64_t n);  // device scratch of one rendering of n 
 // exceeds cap.  max_blocks as for trav_launch_gather_path.
 int trav_launch_dump_path(TravGraph G, const uint32_t *seq_v, const uint32_t *seq_s, uint64_t len, uint32_t k, const DumpTables &T, void *scratch,
                           char *out, uint64_t cap, uint64_t *total_host, hipStream_t s, unsigned max_blocks);
+
+// ---- the consensus sequence of a path (k5_seq.hip) -------------------------------------------------------------------
+// PAlgorithm::seqToString from the records of a path: the bases of its steps, read out of the packed contigs and references
+// where a step is longer than k.  The packed sequences of both coordinate spaces on the device, one blob:
+// [coff u64 x nc][roff u64 x nr][contigs' packed bytes, padded to 16][references' packed bytes]; the lengths are DumpTables'
+// csize / rsize.
+struct SeqSources {
+    const uint64_t *coff, *roff;
+    const uint8_t *cpacked, *rpacked;
+};
+bool seqs_well_formed(const pag_seqs *q);  // arrays present, every sequence inside the packed bytes: what the two below rely on
+size_t seq_sources_bytes(const pag_seqs *ctgs, const pag_seqs *refs);
+// the blob's upload (asynchronous on s: the callers' arrays must stay until the stream has been waited for)
+int seq_sources_upload(void *dev, const pag_seqs *ctgs, const pag_seqs *refs, SeqSources *out, hipStream_t s);
+struct SeqParams {
+    uint32_t k;
+    uint64_t deviation;
+    double error_rate;
+};
+size_t seq_scratch_bytes(uint64_t n);  // device scratch of one rendering of n vertices (256-byte multiple)
+// the sequence of a path (new ids + steps, as trav_launch_gather_path takes them) into `out` (device or pinned host memory).
+// head_host (pinned, may be null): [0] receives the text's size — nothing is written when it exceeds cap — and [1] becomes
+// non-zero when the path is not renderable (a rounded position negative or not finite: what `out` holds then means nothing).
+int trav_launch_seq_path(TravGraph G, const uint32_t *seq_v, const uint32_t *seq_s, uint64_t len, const SeqParams &P, const DumpTables &T,
+                         const SeqSources &S, void *scratch, char *out, uint64_t cap, uint64_t *head_host, hipStream_t s, unsigned max_blocks);
 
 }  // namespace pagdev

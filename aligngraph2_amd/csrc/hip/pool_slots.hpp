@@ -118,6 +118,7 @@ enum Id : int {
     WALK_CJ,                                // jobs of the node-table launch (setup_contigs)
     WALK_CKREQ, WALK_CKOUT,                 // checkpoint and id-bound queries and their answers
     WALK_FIN,                               // the epilogue's undelivered paths (ids, steps)
+    WALK_SEQS,                              // PAG_TRAVEL_RENDER_SEQS: the packed contigs and references with their byte offsets (k5_seq.hip SeqSources)
 
     // ---- selection (pag_shard_select, k_select.hip): a selection lives here until the next one
     SEL_CIV, SEL_RIV,                       // the region's contig intervals and reference bands (uploaded)
@@ -141,7 +142,7 @@ static_assert(PREP_DB_LAST + 1 == IN_ROFF && IMPORT_LAST + 1 == TG_NCODE && SEL_
               "a family's members lie between its base and the next entry");
 
 // pag_shard_release_build hands back everything but the imported graph and the traversal's (graph and session) slots
-constexpr bool released_after_import(Id s) { return s < IMPORT || s > WALK_FIN; }
+constexpr bool released_after_import(Id s) { return s < IMPORT || s > WALK_SEQS; }
 
 // Build buffers the traversal graph's sorts may BORROW (Lender, trav_prepare_graph): between two pag_process calls they are
 // idle unless the finished graph points into them.  A loan never grows a slot; ties go to the earlier entry.

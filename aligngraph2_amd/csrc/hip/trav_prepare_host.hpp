@@ -118,6 +118,7 @@ struct CtgState {
         uint32_t *d_ids = nullptr;  // ids at [0, cap), steps at [cap, 2 cap); the tail from entry m0 on
         size_t cap = 0, m0 = 0, n = 0;
         uint32_t last_ctg = 0;      // coordinate of the tail's last vertex (the "Pump it" test)
+        uint64_t step_bound = 0;    // at least the sum of the positive steps of the tail's vertices (PAG_TRAVEL_RENDER_SEQS sizes the text by it)
     } tail;
 };
 

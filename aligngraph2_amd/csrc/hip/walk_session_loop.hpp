@@ -450,6 +450,9 @@ struct WalkSession : WalkRounds {
                         T.m0 = at0;
                         T.n = P.len;
                         T.last_ctg = ch.parts.back().pc[ch.parts.back().n - 1];
+                        T.step_bound = ch.size + (uint64_t)(dist > 0 ? dist : 0);  // (the chain's steps, its first one replaced by dist.  A bound of the POSITIVE steps because no step of a walk is negative:
+                        // they are the successor records' steps, an unsigned 24-bit field of SuccRec::meta.  Were one ever negative the text
+                        // would exceed its buffer, nothing would be written and the host would render that path)
                         for (size_t x = 0; x < ch.parts.size(); ++x) cp[x] = TravConcatPart{ch.parts[x].dv, ch.parts[x].ds, ch.parts[x].start, ch.parts[x].n};
                         if (!g->deliver_stream && hipStreamCreateWithFlags(&g->deliver_stream, hipStreamNonBlocking) != hipSuccess) return fail(PAG_EFAULT);
                         trav_launch_concat_parts(cp, (uint32_t)ch.parts.size(), T.d_ids + at0, T.d_ids + cap + at0, (uint32_t)dist, g->deliver_stream);
@@ -825,7 +828,7 @@ struct WalkSession : WalkRounds {
             for (auto &cs : st) {
                 if (cs.delivered) continue;
                 const size_t slot2 = 2 * (size_t)cs.ci + (cs.forward ? 0 : 1);
-                if (render && !cs.travel.empty()) scratch_bytes += dump_scratch_bytes(cs.travel.size());
+                if (!cs.travel.empty()) scratch_bytes += render_scratch_bytes(cs.travel.size());
                 g->path_off[slot2] = at;
                 g->path_len[slot2] = cs.travel.size();
                 g->path_valid[slot2] = 1;
@@ -842,7 +845,7 @@ struct WalkSession : WalkRounds {
                 trav_launch_gather_path(G, b_fin.as<uint32_t>(), b_fin.as<uint32_t>() + tot, tot, b_gather.as<pag_path_node>(), s);
                 PAG_HIP_TRY(hipMemcpyAsync(g->path_store, b_gather.p, tot * sizeof(pag_path_node), hipMemcpyDeviceToHost, s));
             }
-            if (render && scratch_bytes) {  // the dump text of those sequences: one rendering per contig, at full width (no walk is live)
+            if (scratch_bytes) {  // the dump text and the consensus sequence of those sequences: one rendering per contig, at full width (no walk is live)
                 if (g->dump_scratch_cap < scratch_bytes) {
                     if (g->dump_scratch) PAG_HIP_TRY(hipFree(g->dump_scratch));
                     g->dump_scratch = nullptr;
@@ -855,9 +858,16 @@ struct WalkSession : WalkRounds {
                     if (cs.delivered || cs.travel.empty()) continue;
                     const size_t slot2 = 2 * (size_t)cs.ci + (cs.forward ? 0 : 1);
                     const uint32_t *ids = b_fin.as<uint32_t>() + g->path_off[slot2];
-                    if ((rc = render_path(slot2, ids, ids + tot, cs.travel.size(), (char *)g->dump_scratch + sat, s, 0u))) return fail(rc);
-                    ++n_epilogue_texts;
-                    sat += dump_scratch_bytes(cs.travel.size());
+                    if (render) {
+                        if ((rc = render_path(slot2, ids, ids + tot, cs.travel.size(), (char *)g->dump_scratch + sat, s, 0u))) return fail(rc);
+                        ++n_epilogue_texts;
+                        sat += dump_scratch_bytes(cs.travel.size());
+                    }
+                    if (render_seq) {
+                        if ((rc = render_seq_path(slot2, ids, ids + tot, cs.travel.size(), travel_bases(cs.travel, k), (char *)g->dump_scratch + sat, s, 0u))) return fail(rc);
+                        ++n_epilogue_seqs;
+                        sat += seq_scratch_bytes(cs.travel.size());
+                    }
                 }
             }
             PAG_HIP_TRY(hipStreamSynchronize(s));
@@ -870,6 +880,14 @@ struct WalkSession : WalkRounds {
                     if (g->path_len[slot2]) (g->text_ptr[slot2] ? n_text : n_none) += 1;
                 }
                 std::fprintf(stderr, "[timing] dump text: %zu contigs rendered (%zu of them in the epilogue), %zu left to the host\n", n_text, n_epilogue_texts, n_none);
+            }
+            if (timing && render_seq) {
+                size_t n_text = 0, n_none = 0;
+                for (auto &cs : st) {
+                    const size_t slot2 = 2 * (size_t)cs.ci + (cs.forward ? 0 : 1);
+                    if (g->path_len[slot2]) (g->seq_ptr[slot2] ? n_text : n_none) += 1;
+                }
+                std::fprintf(stderr, "[timing] sequence text: %zu paths rendered (%zu of them in the epilogue), %zu left to the host\n", n_text, n_epilogue_seqs, n_none);
             }
         }
         lap("epilogue");

@@ -322,7 +322,10 @@ struct WalkRounds : WalkJobs {
         std::fill(g->path_ptr.begin(), g->path_ptr.end(), nullptr);
         std::fill(g->text_ptr.begin(), g->text_ptr.end(), nullptr);
         std::fill(g->text_len.begin(), g->text_len.end(), (uint64_t)0);
+        std::fill(g->seq_ptr.begin(), g->seq_ptr.end(), nullptr);
+        std::fill(g->seq_len.begin(), g->seq_len.end(), (uint64_t)0);
         text_pending.clear();
+        seq_pending.clear();
         return rc2;
     }
 
@@ -373,9 +376,22 @@ struct WalkRounds : WalkJobs {
     };
     std::vector<TextPending> text_pending;
     size_t n_epilogue_texts = 0;
+    // PAG_TRAVEL_RENDER_SEQS: the consensus sequence of every delivered path (k5_seq.hip), the same way.  Its size is known
+    // before the launch — k + the positive steps, which this thread has (the tail of a path put together on the device: a bound
+    // from its chain's step sum) — and sizes the buffer; the device's own count and its "not renderable" flag arrive in front
+    // of the text (resolve_texts).  Needs the references' bases (pag_travel_seq_sources): without them nothing is rendered.
+    bool render_seq = false;
+    SeqSources seq_src{};
+    std::vector<TextPending> seq_pending;  // buf: [u64 size][u64 not renderable, padding to 256][text]
+    size_t n_epilogue_seqs = 0;
     int setup_render() {
-        render = false;
-        if (!(prm->reserved & PAG_TRAVEL_RENDER_DUMPS) || !dump_tables_build(ctgs->len, ctgs->n_seqs, ref_len, n_refs, dump_blob)) return PAG_OK;
+        render = render_seq = false;
+        const bool want_dumps = (prm->reserved & PAG_TRAVEL_RENDER_DUMPS) != 0;
+        const pag_seqs *refs = g->seq_refs;
+        // (a table that is not well formed — a sequence beyond its packed bytes — renders nothing: the kernels trust the offsets)
+        bool want_seqs = (prm->reserved & PAG_TRAVEL_RENDER_SEQS) != 0 && refs && refs->n_seqs == n_refs && seqs_well_formed(refs) && seqs_well_formed(ctgs);
+        for (uint64_t r = 0; want_seqs && r < n_refs; ++r) want_seqs = refs->len[r] == ref_len[r];
+        if ((!want_dumps && !want_seqs) || !dump_tables_build(ctgs->len, ctgs->n_seqs, ref_len, n_refs, dump_blob)) return PAG_OK;
         const size_t bytes = dump_blob.size() * 4 + 16;
         if (g->dump_tables_cap < bytes) {
             if (g->dump_tables) PAG_HIP_TRY(hipFree(g->dump_tables));
@@ -387,9 +403,32 @@ struct WalkRounds : WalkJobs {
         if (!dump_blob.empty()) PAG_HIP_TRY(hipMemcpyAsync(g->dump_tables, dump_blob.data(), dump_blob.size() * 4, hipMemcpyHostToDevice, s));
         dump_tab = dump_tables_at((const uint32_t *)g->dump_tables, ctgs->n_seqs, n_refs);
         dump_bound = dump_line_bound(k, dump_blob, ctgs->n_seqs, n_refs);
-        render = true;
+        render = want_dumps;
+        if (want_seqs) {
+            DevBuf b_seqs(g, ps::WALK_SEQS);
+            int rc2;
+            if ((rc2 = b_seqs.alloc(seq_sources_bytes(ctgs, refs))) || (rc2 = seq_sources_upload(b_seqs.p, ctgs, refs, &seq_src, s))) return rc2;
+            render_seq = true;
+        }
         return PAG_OK;
     }
+    // bases: the text's size, or a bound of it
+    int render_seq_path(size_t slot2, const uint32_t *d_v, const uint32_t *d_s, size_t m, uint64_t bases, void *scratch, hipStream_t st, unsigned max_blocks) {
+        char *buf = (char *)fetch_alloc(256 + bases + 16);
+        if (!buf) return PAG_OK;  // (no pinned memory for the text, which is an extra: the caller renders that path itself)
+        ((uint64_t *)buf)[0] = ~0ull;
+        ((uint64_t *)buf)[1] = 0;
+        const SeqParams P{k, (uint64_t)deviation, errorRate};
+        int rc2 = trav_launch_seq_path(G, d_v, d_s, m, P, dump_tab, seq_src, scratch, buf + 256, bases, (uint64_t *)buf, st, max_blocks);
+        if (rc2 == PAG_OK) seq_pending.push_back(TextPending{slot2, buf, bases});
+        return rc2;
+    }
+    static uint64_t travel_bases(const std::vector<LNode> &seq, uint32_t k) {
+        uint64_t b = seq.empty() ? 0 : k;
+        for (size_t x = 1; x < seq.size(); ++x) b += seq[x].step > 0 ? (uint64_t)seq[x].step : 0ull;
+        return b;
+    }
+    size_t render_scratch_bytes(size_t m) const { return (render ? dump_scratch_bytes(m) : 0) + (render_seq ? seq_scratch_bytes(m) : 0); }
     int render_path(size_t slot2, const uint32_t *d_v, const uint32_t *d_s, size_t m, void *scratch, hipStream_t st, unsigned max_blocks) {
         const uint64_t cap = (uint64_t)m * dump_bound;
         char *buf = (char *)fetch_alloc(256 + cap);
@@ -399,8 +438,7 @@ struct WalkRounds : WalkJobs {
         if (rc2 == PAG_OK) text_pending.push_back(TextPending{slot2, buf, cap});
         return rc2;
     }
-    void *arena_scratch(size_t m) {  // (nullptr: no room — that contig's text is left to the caller)
-        const size_t need = dump_scratch_bytes(m);
+    void *arena_scratch(size_t need) {  // (nullptr: no room — that contig's text is left to the caller)
         if (!g->walk_arena || g->walk_arena_used + need > g->walk_arena_cap) return nullptr;
         void *q = (char *)g->walk_arena + g->walk_arena_used;
         g->walk_arena_used += need;
@@ -414,6 +452,13 @@ struct WalkRounds : WalkJobs {
             g->text_len[t.slot2] = total;
         }
         text_pending.clear();
+        for (const TextPending &t : seq_pending) {
+            const uint64_t total = ((const volatile uint64_t *)t.buf)[0], bad = ((const volatile uint64_t *)t.buf)[1];
+            if (total > t.cap || bad) continue;  // (did not fit its bound, or not renderable: the caller renders that path)
+            g->seq_ptr[t.slot2] = t.buf + 256;
+            g->seq_len[t.slot2] = total;
+        }
+        seq_pending.clear();
     }
     int deliver_contig(uint32_t i) {
         CtgState &cs = st[i];
@@ -442,15 +487,22 @@ struct WalkRounds : WalkJobs {
             trav_launch_gather_path(G, T.d_ids, T.d_ids + T.cap, m, dst, g->deliver_stream, n_live ? DELIVER_BLOCKS : 0u);
             g->path_ptr[slot2] = dst;
             if (render) {
-                void *scratch = arena_scratch(m);
+                void *scratch = arena_scratch(dump_scratch_bytes(m));
                 int rc2;
                 if (scratch && (rc2 = render_path(slot2, T.d_ids, T.d_ids + T.cap, m, scratch, g->deliver_stream, n_live ? DELIVER_BLOCKS : 0u))) return rc2;
+            }
+            if (render_seq) {
+                void *scratch = arena_scratch(seq_scratch_bytes(m));
+                uint64_t bases = (uint64_t)k + T.step_bound;  // (a bound: the first vertex counts k, a pumped last vertex nothing)
+                for (size_t x = 0; x < m0; ++x) bases += cs.travel[x].step > 0 ? (uint64_t)cs.travel[x].step : 0ull;
+                int rc2;
+                if (scratch && (rc2 = render_seq_path(slot2, T.d_ids, T.d_ids + T.cap, m, bases, scratch, g->deliver_stream, n_live ? DELIVER_BLOCKS : 0u))) return rc2;
             }
             return PAG_OK;
         }
         if (cfg.debug_deliver_late) return PAG_OK;
         const size_t n = cs.travel.size();
-        const size_t need = ((n * 8 + 255) & ~(size_t)255) + 512 + (render ? dump_scratch_bytes(n) : 0);
+        const size_t need = ((n * 8 + 255) & ~(size_t)255) + 512 + render_scratch_bytes(n);
         if (!g->walk_arena || g->walk_arena_used + need > g->walk_arena_cap) return PAG_OK;
         filter_travel(cs);
         const size_t m = cs.travel.size();
@@ -477,9 +529,15 @@ struct WalkRounds : WalkJobs {
         trav_launch_gather_path(G, d_ids, d_ids + m, m, dst, g->deliver_stream, n_live ? DELIVER_BLOCKS : 0u);
         g->path_ptr[slot2] = dst;
         if (render) {
-            void *scratch = arena_scratch(m);
+            void *scratch = arena_scratch(dump_scratch_bytes(m));
             int rc2;
             if (scratch && (rc2 = render_path(slot2, d_ids, d_ids + m, m, scratch, g->deliver_stream, n_live ? DELIVER_BLOCKS : 0u))) return rc2;
+        }
+        if (render_seq) {
+            void *scratch = arena_scratch(seq_scratch_bytes(m));
+            int rc2;
+            if (scratch && (rc2 = render_seq_path(slot2, d_ids, d_ids + m, m, travel_bases(cs.travel, k), scratch, g->deliver_stream, n_live ? DELIVER_BLOCKS : 0u)))
+                return rc2;
         }
         return PAG_OK;
     }
@@ -537,6 +595,8 @@ struct WalkRounds : WalkJobs {
         g->path_ptr.assign(2 * (size_t)n_ctgs, nullptr);
         g->text_ptr.assign(2 * (size_t)n_ctgs, nullptr);
         g->text_len.assign(2 * (size_t)n_ctgs, 0);
+        g->seq_ptr.assign(2 * (size_t)n_ctgs, nullptr);
+        g->seq_len.assign(2 * (size_t)n_ctgs, 0);
         // one entry per (contig, orientation): a contig selected with both orientations is two independent traversals
         // (PAssembly.cpp:28-36 walks every (name, forward) pair of its set)
         for (uint32_t c2 = 0; c2 < 2 * n_ctgs; ++c2) {

@@ -444,10 +444,33 @@ std::set<std::pair<std::string, bool>> assemble(const std::string &outDir, const
             worker();
             for (auto &t : pool) t.join();
         };
+        // PAGRAPH_DEVICE_SEQS: a piece the device rendered (AssembleShare::seqText) is taken as it is — only if it can be the
+        // sequence of these records: k + the positive steps behind the first vertex is its size; any other piece goes through
+        // seqToString and shows up in the timing line
+        std::atomic<std::uint64_t> devPieces{0}, devBases{0}, hostPieces{0}, hostBases{0};
+        const double tRender = nowMs();
         runPool(nPieces, [&](std::size_t x) {
             const ChainOut &co = chains[pieceOf[x].first];
-            pieces[x] = algo.seqToString(results[co.order[pieceOf[x].second]], deviation, errorRate);
+            const std::size_t slot = co.order[pieceOf[x].second];
+            const TravelSequence &seq = results[slot];
+            if (share && share->seqText && slot < share->seqText->size() && (*share->seqText)[slot].first && !seq.empty()) {
+                std::uint64_t want = graph.k;
+                for (std::size_t v = 1; v < seq.size(); ++v) want += static_cast<std::uint64_t>(std::max(seq[v].second, 0));
+                if ((*share->seqText)[slot].second == want) {
+                    pieces[x].assign((*share->seqText)[slot].first, static_cast<std::size_t>(want));
+                    devPieces += 1;
+                    devBases += want;
+                    return;
+                }
+            }
+            pieces[x] = algo.seqToString(seq, deviation, errorRate);
+            hostPieces += 1;
+            hostBases += pieces[x].size();
         });
+        if (timing)
+            std::fprintf(stderr, "[timing] chain pieces: device-rendered %llu %llu; host-rendered %llu %llu; render %.1f ms\n",
+                         (unsigned long long)devPieces.load(), (unsigned long long)devBases.load(), (unsigned long long)hostPieces.load(),
+                         (unsigned long long)hostBases.load(), nowMs() - tRender);
         runPool(chains.size(), [&](std::size_t c) {
             ChainOut &co = chains[c];
             const std::size_t lineSize = 70;

@@ -39,6 +39,9 @@ struct AssembleShare {
     std::function<bool(std::size_t)> writesDump;
     bool dumpsOnly = false;
     const DumpTexts *dumpText = nullptr;
+    // seqText (PAGRAPH_DEVICE_SEQS): the consensus sequence of that slot's travel sequence as the device rendered it — what
+    // seqToString returns for it; a chain piece without one is rendered by seqToString
+    const DumpTexts *seqText = nullptr;
 };
 std::set<std::pair<std::string, bool>> assemble(const std::string &outDir, const std::string &prefix, const HostGraph &graph,
                                                 const SeqDb &contigs, const SeqDb &refs, const PositionMapper &ctgMapper,

@@ -110,7 +110,9 @@ public:
         buildPathGraph(tv.views, ctx.k, graph, travelled);
         gathered_.swap(tv.gathered);  // (the path graph refers to it)
         texts_.swap(tv.texts);
+        seqs_.swap(tv.seqs);
     }
+    const std::vector<std::pair<const char *, std::uint64_t>> *travelSeqTexts() const override { return seqs_.empty() ? nullptr : &seqs_; }
     const std::vector<std::pair<const char *, std::uint64_t>> *travelDumpTexts() const override { return texts_.empty() ? nullptr : &texts_; }
 
     bool travelsInHalves() const override { return true; }
@@ -148,12 +150,22 @@ public:
         pag_seqs cs{contigs.size(), contigs.byteOff().data(), contigs.lens().data(), contigs.packed().data(), contigs.packed().size()};
         pag_travel_params asked = params;
         if (envDeviceDumps()) asked.reserved |= PAG_TRAVEL_RENDER_DUMPS;
+        // (a sharded run: rank 0 builds the chains from the gathered paths of all ranks and renders their pieces on the host)
+        const bool deviceSeqs = envDeviceSeqs() && !comm_;
+        const SeqDb &refs = ctx.refs;
+        pag_seqs rs{refs.size(), refs.byteOff().data(), refs.lens().data(), refs.packed().data(), refs.packed().size()};
+        if (deviceSeqs) {
+            asked.reserved |= PAG_TRAVEL_RENDER_SEQS;
+            check(pag_travel_seq_sources(g_, &rs), "pag_travel_seq_sources");
+        }
         check(pag_travel(g_, &cs, orient.data(), refLen.data(), refLen.size(), &asked, nullptr), "pag_travel");
         std::vector<std::pair<const pag_path_node *, std::uint64_t>> &views = out.views;
         std::vector<char> &gathered = out.gathered;
         views.assign(2 * contigs.size(), {nullptr, 0});
         out.texts.clear();
         if (envDeviceDumps()) out.texts.assign(2 * contigs.size(), {nullptr, 0});
+        out.seqs.clear();
+        if (deviceSeqs) out.seqs.assign(2 * contigs.size(), {nullptr, 0});
         for (std::uint64_t c = 0; c < contigs.size(); ++c)
             for (int rev = 0; rev < 2; ++rev) {
                 std::uint64_t len = 0;
@@ -163,6 +175,11 @@ public:
                     std::uint64_t bytes = 0;
                     const char *t = pag_travel_dump_text(g_, c, rev == 0, &bytes);
                     if (t && bytes) out.texts[2 * c + rev] = {t, bytes};
+                }
+                if (p && len && deviceSeqs) {
+                    std::uint64_t bytes = 0;
+                    const char *t = pag_travel_seq_text(g_, c, rev == 0, &bytes);
+                    if (t && bytes) out.seqs[2 * c + rev] = {t, bytes};
                 }
             }
         if (comm_) {
@@ -229,6 +246,7 @@ private:
     unsigned rank_ = 0, world_ = 1;
     ShardPlan plan_;
     std::vector<std::pair<const char *, std::uint64_t>> texts_;  // PAGRAPH_DEVICE_DUMPS: the dump bodies of the last travel()
+    std::vector<std::pair<const char *, std::uint64_t>> seqs_;   // PAGRAPH_DEVICE_SEQS: the consensus sequences of the last travel()
     std::vector<char> gathered_;  // rank 0: the travel sequences of all ranks (the path graph refers to them)
 };
 

@@ -23,6 +23,13 @@ inline bool envDeviceDumps() {
     static const bool on = envInt("PAGRAPH_DEVICE_DUMPS", 0) == 1;
     return on;
 }
+// PAGRAPH_DEVICE_SEQS=1: the consensus sequence of every walked path (the pieces of the chains' .fasta files) is rendered on the
+// device as the walks deliver the paths (pag_travel, PAG_TRAVEL_RENDER_SEQS); read once, independent of PAGRAPH_DEVICE_DUMPS.
+// Unset: SeqTools::seqToString renders them on host threads.
+inline bool envDeviceSeqs() {
+    static const bool on = envInt("PAGRAPH_DEVICE_SEQS", 0) == 1;
+    return on;
+}
 // PAGH_OVERLAP_THREADS=<n>: host threads of a block's host half while it runs beside the next block's device work (0: not given)
 inline unsigned envOverlapThreads() {
     const char *e = std::getenv("PAGH_OVERLAP_THREADS");

@@ -379,8 +379,9 @@ int runPagraph(int argc, char **argv, GraphBackend &backend) {
                 }
                 AssembleShare share;
                 share.dumpText = backend.travelDumpTexts();
+                share.seqText = backend.travelSeqTexts();
                 auto successCtg = assemble(opt.out, prefix, graphs[0], contigs, refs, ctgMapper, refMapper, usedCtg, opt.epsilon * 2, errorRate,
-                                           startSplit, opt.minLen, opt.threads, 0, nullptr, false, precomputed[0], nullptr, share.dumpText ? &share : nullptr);
+                                           startSplit, opt.minLen, opt.threads, 0, nullptr, false, precomputed[0], nullptr, share.dumpText || share.seqText ? &share : nullptr);
                 lap("traverse + write");
                 ++blockNo;
                 for (auto &s : successCtg) okCtg.emplace(s.first);
@@ -437,8 +438,9 @@ int runPagraph(int argc, char **argv, GraphBackend &backend) {
                     if (rankDumps) share.writesDump = [&walkedHere](std::size_t id) { return id < walkedHere.size() && walkedHere[id] != 0; };
                     // (the text lives as long as the travel sequences: until the walks of the block after this one, which wait for this thread)
                     if (!tviews[slot].texts.empty()) share.dumpText = &tviews[slot].texts;
+                    if (!tviews[slot].seqs.empty()) share.seqText = &tviews[slot].seqs;
                     return assemble(opt.out, prefix, graphs[slot], contigs, refs, cm, rm, usedCtg, opt.epsilon * 2, errorRate, startSplit, opt.minLen,
-                                    opt.threads, poolThreads, nullptr, false, precomputed[slot], &half.log, rankDumps || share.dumpText ? &share : nullptr);
+                                    opt.threads, poolThreads, nullptr, false, precomputed[slot], &half.log, rankDumps || share.dumpText || share.seqText ? &share : nullptr);
                 });
                 ++blockNo;
             }

@@ -63,7 +63,10 @@ public:
         std::vector<std::pair<const pag_path_node *, std::uint64_t>> views;  // 2 * contig + (reverse ? 1 : 0)
         std::vector<char> gathered;                                          // (a sharded run: what the other ranks sent)
         std::vector<std::pair<const char *, std::uint64_t>> texts;           // PAGRAPH_DEVICE_DUMPS: dump bodies of the contigs walked here
+        std::vector<std::pair<const char *, std::uint64_t>> seqs;            // PAGRAPH_DEVICE_SEQS: consensus sequences of the paths walked here
     };
+    // PAGRAPH_DEVICE_SEQS: the consensus sequences the last travel() left (null: none; valid until the next travel)
+    virtual const std::vector<std::pair<const char *, std::uint64_t>> *travelSeqTexts() const { return nullptr; }
     // PAGRAPH_DEVICE_DUMPS: the dump bodies the last travel() left (null: none; valid until the next travel)
     virtual const std::vector<std::pair<const char *, std::uint64_t>> *travelDumpTexts() const { return nullptr; }
     virtual bool travelsInHalves() const { return false; }

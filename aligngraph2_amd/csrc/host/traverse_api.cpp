@@ -61,6 +61,8 @@ struct HandleCache {
     std::vector<std::uint64_t> lens;
     std::vector<const char *> texts;  // PAGRAPH_DEVICE_DUMPS: the dump bodies pag_travel rendered (empty: not asked for)
     std::vector<std::uint64_t> textLens;
+    std::vector<const char *> seqs;  // PAGRAPH_DEVICE_SEQS: the consensus sequences pag_travel rendered (empty: not asked for)
+    std::vector<std::uint64_t> seqLens;
     double tBegin = 0, tHost = 0;
     pag_travel_stats tst{};
 };
@@ -101,7 +103,16 @@ int pagh_assemble_paths_text(pag_graph *cache_key, uint32_t k, const pag_seqs *c
                              const uint64_t *path_len, const char *const *dump_text, const uint64_t *dump_text_len, uint32_t ref_threads,
                              uint64_t epsilon, uint64_t min_len, const char *out_dir, const char *prefix, uint32_t host_threads,
                              pagh_traverse_stats *stats) {
-    if (!ctgs || !refs || !ctg_orient || !out_dir || !paths || !path_len || (dump_text && !dump_text_len)) return PAG_EINVAL;
+    return pagh_assemble_paths_seq(cache_key, k, ctgs, ctg_names, refs, ref_names, ctg_orient, paths, path_len, dump_text, dump_text_len, nullptr, nullptr,
+                                   ref_threads, epsilon, min_len, out_dir, prefix, host_threads, stats);
+}
+
+int pagh_assemble_paths_seq(pag_graph *cache_key, uint32_t k, const pag_seqs *ctgs, const char *const *ctg_names, const pag_seqs *refs,
+                            const char *const *ref_names, const int32_t *ctg_orient, const pag_path_node *const *paths,
+                            const uint64_t *path_len, const char *const *dump_text, const uint64_t *dump_text_len, const char *const *seq_text,
+                            const uint64_t *seq_text_len, uint32_t ref_threads, uint64_t epsilon, uint64_t min_len, const char *out_dir,
+                            const char *prefix, uint32_t host_threads, pagh_traverse_stats *stats) {
+    if (!ctgs || !refs || !ctg_orient || !out_dir || !paths || !path_len || (dump_text && !dump_text_len) || (seq_text && !seq_text_len)) return PAG_EINVAL;
     try {
         const double t0 = nowMs();
         pagh::SeqDb contigDb = fromPacked(ctgs, ctg_names, "ctg", 0);
@@ -125,7 +136,7 @@ int pagh_assemble_paths_text(pag_graph *cache_key, uint32_t k, const pag_seqs *c
         const double t1 = nowMs();
         if (pagh::envTiming()) std::fprintf(stderr, "[timing] buildPathGraph %.1f ms\n", t1 - tg0);
         pagh::AssembleStats as;
-        pagh::DumpTexts texts;
+        pagh::DumpTexts texts, seqs;
         pagh::AssembleShare share;
         if (dump_text) {
             texts.assign(2 * ctgs->n_seqs, {nullptr, 0});
@@ -133,8 +144,14 @@ int pagh_assemble_paths_text(pag_graph *cache_key, uint32_t k, const pag_seqs *c
                 if (dump_text[c] && dump_text_len[c] && views[c].second) texts[c] = {dump_text[c], dump_text_len[c]};
             share.dumpText = &texts;
         }
+        if (seq_text) {
+            seqs.assign(2 * ctgs->n_seqs, {nullptr, 0});
+            for (std::uint64_t c = 0; c < 2 * ctgs->n_seqs; ++c)
+                if (seq_text[c] && seq_text_len[c] && views[c].second) seqs[c] = {seq_text[c], seq_text_len[c]};
+            share.seqText = &seqs;
+        }
         pagh::assemble(out_dir, prefix ? prefix : "0_", hc.graph, contigDb, refDb, ctgMapper, refMapper, ctgSet, epsilon * 2, 0.15,
-                       0.90, min_len, ref_threads, host_threads, &as, true, hc.travelled, nullptr, dump_text ? &share : nullptr);
+                       0.90, min_len, ref_threads, host_threads, &as, true, hc.travelled, nullptr, dump_text || seq_text ? &share : nullptr);
         const double t2 = nowMs();
         if (stats) {
             stats->n_contigs = as.nContigs;
@@ -169,6 +186,8 @@ static int traverse_begin(pag_graph *g, uint32_t k, const pag_seqs *ctgs, const 
     tp.min_len = min_len;
     const bool deviceDumps = pagh::envDeviceDumps();
     if (deviceDumps) tp.reserved |= PAG_TRAVEL_RENDER_DUMPS;
+    const bool deviceSeqs = pagh::envDeviceSeqs();
+    if (deviceSeqs) tp.reserved |= PAG_TRAVEL_RENDER_SEQS;
     // the traversal's view of the new graph (successor records: device work, this thread only waits) still runs beside the
     // previous block's host half ...
     double msPrep = 0;
@@ -188,6 +207,7 @@ static int traverse_begin(pag_graph *g, uint32_t k, const pag_seqs *ctgs, const 
         return hc.rc;
     }
     hc.tst = pag_travel_stats{};
+    if (deviceSeqs) pag_travel_seq_sources(g, refs);  // (the references' bases: pag_travel's signature has only their lengths)
     rc = pag_travel(g, ctgs, ctg_orient, refs->len, refs->n_seqs, &tp, &hc.tst);
     const double tC = nowMs();
     hc.tst.ms_compact += msPrep;
@@ -210,11 +230,18 @@ static int traverse_begin(pag_graph *g, uint32_t k, const pag_seqs *ctgs, const 
         hc.texts.assign(2 * ctgs->n_seqs, nullptr);
         hc.textLens.assign(2 * ctgs->n_seqs, 0);
     }
+    hc.seqs.clear();
+    hc.seqLens.clear();
+    if (deviceSeqs) {
+        hc.seqs.assign(2 * ctgs->n_seqs, nullptr);
+        hc.seqLens.assign(2 * ctgs->n_seqs, 0);
+    }
     for (std::uint64_t c = 0; c < ctgs->n_seqs; ++c)
         for (int rev = 0; rev < 2; ++rev) {
             std::uint64_t len = 0;
             const pag_path_node *p = pag_travel_path_oriented(g, c, rev == 0, &len);
             if (p && len) {
+                if (deviceSeqs) hc.seqs[2 * c + rev] = pag_travel_seq_text(g, c, rev == 0, &hc.seqLens[2 * c + rev]);
                 hc.paths[2 * c + rev] = p;
                 hc.lens[2 * c + rev] = len;
                 if (deviceDumps) hc.texts[2 * c + rev] = pag_travel_dump_text(g, c, rev == 0, &hc.textLens[2 * c + rev]);
@@ -245,9 +272,10 @@ static int traverse_begin(pag_graph *g, uint32_t k, const pag_seqs *ctgs, const 
         poolThreads = asked ? asked : std::min(20u, std::max(4u, pagh::usableCpus()));  // (ranks of a node share its cores: host_threads.hpp)
     }
     hc.worker = std::thread([=]() {
-        h->rc = pagh_assemble_paths_text(g, k, ctgs, ctg_names, refs, ref_names, ctg_orient, h->paths.data(), h->lens.data(),
-                                         h->texts.empty() ? nullptr : h->texts.data(), h->texts.empty() ? nullptr : h->textLens.data(), ref_threads,
-                                         epsilon, min_len, outDir.c_str(), pre.c_str(), poolThreads, &h->stats);
+        h->rc = pagh_assemble_paths_seq(g, k, ctgs, ctg_names, refs, ref_names, ctg_orient, h->paths.data(), h->lens.data(),
+                                        h->texts.empty() ? nullptr : h->texts.data(), h->texts.empty() ? nullptr : h->textLens.data(),
+                                        h->seqs.empty() ? nullptr : h->seqs.data(), h->seqs.empty() ? nullptr : h->seqLens.data(), ref_threads, epsilon,
+                                        min_len, outDir.c_str(), pre.c_str(), poolThreads, &h->stats);
         if (h->rc != PAG_OK) h->error = g_err;  // (this thread's message)
     });
     return PAG_OK;

@@ -29,6 +29,7 @@ extern "C" {
 #define PAG_ENODEV (-19)  /* no usable HIP device */
 #define PAG_ERANGE (-34)  /* caller buffer too small; required sizes are reported */
 #define PAG_EFAULT (-14)  /* a HIP runtime call or kernel failed; see pag_last_error() */
+#define PAG_EDOM (-33)    /* pag_render_path_sequence: the path is not renderable (see there); nothing was written */
 
 #define PAG_NONE 0xFFFFFFFFu
 
@@ -438,6 +439,39 @@ int pag_reserve_walk_arena(pag_graph *g, uint64_t contig_bases);
 int pag_render_dump_lines(const pag_path_node *records, uint64_t n, uint32_t k, const uint32_t *ctg_len, uint64_t n_ctgs,
                           const uint32_t *ref_len, uint64_t n_refs, char *out, uint64_t cap, uint64_t *bytes, int device);
 const char *pag_travel_dump_text(const pag_graph *g, uint64_t ctg_index, int forward, uint64_t *bytes);
+/* ---- the consensus sequence of a path, rendered on the device (csrc/hip/k5_seq.hip) ---------------------------------------
+ * PAlgorithm::seqToString (PAlgorithm.cpp:428-489) from pag_path_node records: the k-mer of record 0, then per record with
+ * step s: the last s bases of its k-mer in upper case when s <= k (nothing for s <= 0); else s - k bases in lower case read
+ * from a contig or a reference sequence — isEdgeSimilar / isPosSimilar (PABruijnGraph.cpp:379-400) of the previous record's
+ * coordinates and its own choose the space, singleToDual of both ends the sequence, the strand and the slope, the position
+ * is an f64 accumulated one addition per base and rounded half away from zero — followed by its whole k-mer.  A position past
+ * the end of its sequence, or a sequence index outside the table (coordinate 0), gives 'n'.  The size of the text is
+ * k + the sum of the positive steps behind record 0.
+ * NOT RENDERABLE: a rounded position that is negative or not finite (the reference casts it to size_t: undefined).  The
+ * device does not guess: pag_render_path_sequence returns PAG_EDOM and writes nothing (*bytes still holds the size),
+ * pag_travel hands out no text for that path; the caller renders it itself.
+ *
+ * pag_render_path_sequence: the sequence for n records in HOST memory into the caller's buffer; ctgs / refs: the packed
+ * sequences of both coordinate spaces (host memory).  *bytes receives the size the text takes whenever the arguments are
+ * accepted (also without a device: it is a sum over the records); PAG_ERANGE when cap is
+ * smaller (nothing is written then), PAG_EINVAL for k outside 1..16, malformed pag_seqs or coordinate spaces beyond 32 bits,
+ * PAG_ENODEV without a gfx950 device (no host fallback behind this call), PAG_EDOM as above.  A utility entry point like
+ * pag_render_dump_lines: every call creates and destroys its stream and device buffers on `device` and waits for the result;
+ * the calling thread's current device is the same after the call as before it.
+ *
+ * pag_travel with PAG_TRAVEL_RENDER_SEQS set in pag_travel_params.reserved renders the sequence of every contig it delivers,
+ * from the records pag_travel_path_oriented returns for it and 1:1 with them, with the call's deviation and error rate.  It
+ * needs the references' bases, which pag_travel's signature does not carry: pag_travel_seq_sources(g, refs) hands them over
+ * (host memory; the POINTER is kept and read by the next pag_travel on the handle, which forgets it when it returns; lengths
+ * and count must be those of that call's ref_len).  Without that call the flag does nothing.  pag_travel_seq_text(g, i,
+ * forward, &bytes) returns the text with the contract of pag_travel_dump_text: library-owned PINNED memory with the lifetime
+ * of the path records.  NULL / 0: the orientation was not traversed, its path is empty, rendering was not asked for, the
+ * sources were missing, there was no room in the walk arena or in pinned memory, or the path is not renderable. */
+#define PAG_TRAVEL_RENDER_SEQS 2u
+int pag_render_path_sequence(const pag_path_node *records, uint64_t n, uint32_t k, const pag_seqs *ctgs, const pag_seqs *refs,
+                             uint64_t deviation, double error_rate, char *out, uint64_t cap, uint64_t *bytes, int device);
+int pag_travel_seq_sources(pag_graph *g, const pag_seqs *refs);
+const char *pag_travel_seq_text(const pag_graph *g, uint64_t ctg_index, int forward, uint64_t *bytes);
 /* ---- kmer_counter on the device (replaces PAGraph/src/main/kmer_counter.cpp:19-96) ----------------
  * Counts every k-mer of the forward strand of every read (KmerHelper::kmer2Code, KmerHelper.cpp:7-25) in a dense 4^k
  * table, derives the minimum abundance by the reference's rule (the first occurring abundance a, ascending, with

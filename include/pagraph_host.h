@@ -66,6 +66,18 @@ int pagh_assemble_paths_text(pag_graph *cache_key, uint32_t k, const pag_seqs *c
                              const pag_path_node *const *paths, const uint64_t *path_len, const char *const *dump_text,
                              const uint64_t *dump_text_len, uint32_t ref_threads, uint64_t epsilon, uint64_t min_len,
                              const char *out_dir, const char *prefix, uint32_t host_threads, pagh_traverse_stats *stats);
+/* ... and with the consensus sequences of the paths already rendered (pag_travel with PAG_TRAVEL_RENDER_SEQS after
+ * pag_travel_seq_sources, pag_travel_seq_text): seq_text[2 * c + (reverse ? 1 : 0)] / seq_text_len[...] = the sequence that
+ * belongs to paths[...] (NULL / 0: none — the host renders that piece itself).  A chain's .fasta is then put together from
+ * these buffers; line wrapping, .con and .help stay host code.  seq_text NULL: pagh_assemble_paths_text.  pagh_traverse* ask
+ * for the sequences and pass them on when PAGRAPH_DEVICE_SEQS=1 is in the environment (read once); the files are the same
+ * bytes either way. */
+int pagh_assemble_paths_seq(pag_graph *cache_key, uint32_t k, const pag_seqs *ctgs, const char *const *ctg_names,
+                            const pag_seqs *refs, const char *const *ref_names, const int32_t *ctg_orient,
+                            const pag_path_node *const *paths, const uint64_t *path_len, const char *const *dump_text,
+                            const uint64_t *dump_text_len, const char *const *seq_text, const uint64_t *seq_text_len,
+                            uint32_t ref_threads, uint64_t epsilon, uint64_t min_len, const char *out_dir, const char *prefix,
+                            uint32_t host_threads, pagh_traverse_stats *stats);
 /* Drops the host storage kept for a graph handle between pagh_traverse calls; waits for a host half still running.  Call it
  * before pag_destroy of a handle that was traversed. */
 void pagh_release(pag_graph *g);
