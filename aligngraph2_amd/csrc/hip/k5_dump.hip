@@ -5,31 +5,25 @@
 //     <KMER>,<ctg>,<ref>,<cnt>\t<step>\t<cIdx>,<cOff>\t<rIdx>,<rOff>\n
 // with (cIdx, cOff) / (rIdx, rOff) = PositionMapper::singleToDual over the contigs / the references.
 //
-// Two launches.  k_dump_measure: a thread per vertex computes its line's length, a tile of 256 lines leaves its byte count,
-// and the block that finishes last scans the tile counts into byte offsets and the total.  k_dump_render: a tile's threads
-// format their lines into an LDS staging buffer at their prefix offsets, then the block copies the staged bytes to the output
-// with 16-byte stores (the tile's unaligned head and tail byte by byte).  The output may be pinned host memory: what
-// reaches it are whole 16-byte stores of consecutive lanes.
-//
-// The lines are formatted from pag_path_node values by functions that know nothing of the graph; the records come either from
-// an array (pag_render_dump_lines) or from the traversal view and a path's vertex ids (pag_travel's deliveries, where they are
-// the records k_gather_path writes).
+// Two launches over tiles of 256 lines, k_dump_measure and k_dump_render: the skeleton they share with the consensus
+// sequence's renderer (k5_seq.hip) is text_tiles.hpp — measure and scan, staging, the copy-out, the sources of the records.
+// The lines are formatted from a vertex's values by functions that know nothing of the graph.
 #include <algorithm>
 #include <vector>
 
 #include "pag_device.hpp"
 #include "pag_travel.hpp"
+#include "text_tiles.hpp"
 
 namespace pagdev {
 
 namespace {
 
-constexpr uint32_t DUMP_TILE = 256;
 // the longest line: k = 16, two 10-digit coordinates, a 5-digit count, an 11-character step, and per coordinate space an index
 // of at most 10 and an offset of at most 11 characters (dump_tables_build keeps the tables inside those bounds), 9 separators
 constexpr uint32_t DUMP_MAX_LINE = 16 + 10 + 10 + 5 + 11 + 2 * (10 + 11) + 9;
 static_assert(DUMP_MAX_LINE == 103, "line bound");
-constexpr uint32_t DUMP_STAGE_BYTES = DUMP_TILE * 104 + 16;  // (+ 16: a tile is staged at the output's alignment)
+constexpr uint32_t DUMP_STAGE_BYTES = TEXT_TILE * 104 + 16;  // (+ 16: a tile is staged at the output's alignment)
 
 struct DumpFields {
     uint32_t code, ctg, ref, cnt;
@@ -105,29 +99,6 @@ __device__ __forceinline__ void dump_line_write(unsigned char *stage, uint32_t a
     }
 }
 
-// where the records come from
-struct DumpSrcRecords {
-    const pag_path_node *rec;
-    __device__ __forceinline__ pag_path_node operator()(uint64_t i) const { return rec[i]; }
-};
-struct DumpSrcPath {  // what k_gather_path (k5_walk_aux.hip) writes for entry i of a path
-    TravGraph G;
-    const uint32_t *seq_v, *seq_s;
-    __device__ __forceinline__ pag_path_node operator()(uint64_t i) const {
-        const uint32_t v = G.uold[seq_v[i]];
-        const uint64_t p = G.vpos[v];
-        pag_path_node o;
-        o.code = G.ncode[G.vnode[v]];
-        o.ctg = (uint32_t)(p >> 32);
-        o.ref = (uint32_t)p;
-        o.cnt = G.vcnt[v];
-        o.reserved = 0;
-        o.step = (int32_t)seq_s[i];
-        o.vid = v;
-        return o;
-    }
-};
-
 // the start tables of both coordinate spaces in LDS when they fit (DUMP_LDS_STARTS entries), else where they are
 template <bool LDS_T>
 struct StartTables {
@@ -149,7 +120,7 @@ struct StartTables {
 
 template <typename Src, bool LDS_T>
 __device__ __forceinline__ DumpFields dump_fields(const Src &src, uint64_t i, const DumpTables &T, const uint32_t *cst, const uint32_t *rst) {
-    const pag_path_node n = src(i);
+    const PathVertex n = src(i);
     DumpFields f;
     f.code = n.code;
     f.ctg = n.ctg;
@@ -163,132 +134,52 @@ __device__ __forceinline__ DumpFields dump_fields(const Src &src, uint64_t i, co
 
 // byte count of every tile of 256 lines; the last block to finish turns them into byte offsets and the total
 template <typename Src, bool LDS_T>
-__global__ void __launch_bounds__(DUMP_TILE) k_dump_measure(Src src, uint64_t n, uint32_t k, DumpTables T, uint32_t *__restrict__ tile_cnt,
+__global__ void __launch_bounds__(TEXT_TILE) k_dump_measure(Src src, uint64_t n, uint32_t k, DumpTables T, uint64_t *__restrict__ tile_cnt,
                                                             uint64_t *__restrict__ tile_off, uint32_t *ticket, uint64_t *total_dev,
                                                             uint64_t *total_host) {
     __shared__ uint32_t tab[LDS_T ? DUMP_LDS_STARTS : 1];
-    __shared__ uint64_t wsum[DUMP_TILE / PAG_WAVE];
-    __shared__ uint32_t last;
     const StartTables<LDS_T> st(T, tab);
-    const uint64_t n_tiles = (n + DUMP_TILE - 1) / DUMP_TILE;
-    const uint32_t wave = threadIdx.x / PAG_WAVE;
-    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const uint64_t i = tile * DUMP_TILE + threadIdx.x;
-        uint32_t len = 0;
-        if (i < n) len = dump_line_len(dump_fields<Src, LDS_T>(src, i, T, st.c, st.r), k);
-        const uint32_t w = wave_sum(len);
-        if (lane_id() == 0) wsum[wave] = w;
-        __syncthreads();
-        if (threadIdx.x == 0) tile_cnt[tile] = (uint32_t)(wsum[0] + wsum[1] + wsum[2] + wsum[3]);
-        __syncthreads();
-    }
-    // the counts of this block are visible device-wide before its ticket is
-    __threadfence();
-    if (threadIdx.x == 0) last = atomicAdd(ticket, 1u) == gridDim.x - 1u;
-    __syncthreads();
-    if (!last) return;
-    __threadfence();
-    uint64_t carry = 0;
-    for (uint64_t base = 0; base < n_tiles; base += DUMP_TILE) {
-        const uint64_t t = base + threadIdx.x;
-        const uint64_t c = t < n_tiles ? (uint64_t)__hip_atomic_load(&tile_cnt[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
-        uint64_t wtot;
-        const uint64_t pre = wave_excl_sum64(c, &wtot);
-        if (lane_id() == 0) wsum[wave] = wtot;
-        __syncthreads();
-        uint64_t before = carry;
-        for (uint32_t w = 0; w < wave; ++w) before += wsum[w];
-        if (t < n_tiles) tile_off[t] = before + pre;
-        carry += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        *total_dev = carry;
-        if (total_host) *total_host = carry;
-    }
+    text_measure(n, [&](uint64_t i) { return dump_line_len(dump_fields<Src, LDS_T>(src, i, T, st.c, st.r), k); }, tile_cnt, tile_off, ticket, total_dev, total_host);
 }
 
 template <typename Src, bool LDS_T>
-__global__ void __launch_bounds__(DUMP_TILE) k_dump_render(Src src, uint64_t n, uint32_t k, DumpTables T, const uint64_t *__restrict__ tile_off,
+__global__ void __launch_bounds__(TEXT_TILE) k_dump_render(Src src, uint64_t n, uint32_t k, DumpTables T, const uint64_t *__restrict__ tile_off,
                                                            const uint64_t *__restrict__ total_dev, unsigned char *out, uint64_t cap) {
     __shared__ __attribute__((aligned(16))) unsigned char stage[DUMP_STAGE_BYTES];
     __shared__ uint32_t tab[LDS_T ? DUMP_LDS_STARTS : 1];
-    __shared__ uint32_t wsum[DUMP_TILE / PAG_WAVE];
     if (*total_dev > cap) return;  // (nothing is written into a buffer that cannot take all of it)
     const StartTables<LDS_T> st(T, tab);
     out = as_global(out);
-    const uint64_t n_tiles = (n + DUMP_TILE - 1) / DUMP_TILE;
-    const uint32_t wave = threadIdx.x / PAG_WAVE;
+    const uint64_t n_tiles = (n + TEXT_TILE - 1) / TEXT_TILE;
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const uint64_t i = tile * DUMP_TILE + threadIdx.x;
+        const uint64_t i = tile * TEXT_TILE + threadIdx.x;
         uint32_t len = 0;
         DumpFields f{};
         if (i < n) {
             f = dump_fields<Src, LDS_T>(src, i, T, st.c, st.r);
             len = dump_line_len(f, k);
         }
-        uint32_t wtot;
-        const uint32_t pre = wave_excl_sum(len, &wtot);
-        if (lane_id() == 0) wsum[wave] = wtot;
-        __syncthreads();
-        uint32_t before = 0;
-        for (uint32_t w = 0; w < wave; ++w) before += wsum[w];
-        const uint32_t tile_bytes = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        // the tile is staged at the alignment its bytes have in the output: 16-byte groups of the one are 16-byte groups of the other
+        uint32_t tile_bytes;
+        const uint32_t at = tile_offset(len, &tile_bytes);
         const uint64_t o = tile_off[tile];
-        const uint32_t sh = (uint32_t)(((uintptr_t)out + o) & 15u);
-        if (i < n) dump_line_write(stage, sh + before + pre, len, f, k);
-        __syncthreads();
-        unsigned char *dst = out + o - sh;  // (16-byte aligned; nothing below dst + sh is touched)
-        const uint32_t lo = sh, hi = sh + tile_bytes;
-        const uint32_t a_lo = (lo + 15u) & ~15u, a_hi = hi & ~15u;
-        if (a_lo >= a_hi) {
-            for (uint32_t j = lo + threadIdx.x; j < hi; j += DUMP_TILE) dst[j] = stage[j];
-        } else {
-            if (lo + threadIdx.x < a_lo) dst[lo + threadIdx.x] = stage[lo + threadIdx.x];
-            for (uint32_t q = (a_lo >> 4) + threadIdx.x; q < (a_hi >> 4); q += DUMP_TILE) ((uint4 *)dst)[q] = ((const uint4 *)stage)[q];
-            if (a_hi + threadIdx.x < hi) dst[a_hi + threadIdx.x] = stage[a_hi + threadIdx.x];
-        }
+        if (i < n) dump_line_write(stage, stage_shift(out, o) + at, len, f, k);
+        tile_flush(stage, out, o, tile_bytes);
         __syncthreads();
     }
 }
-
-unsigned dump_grid(uint64_t n, unsigned max_blocks) {
-    const uint64_t n_tiles = (n + DUMP_TILE - 1) / DUMP_TILE;
-    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(n_tiles, max_blocks ? max_blocks : 1024u));
-}
-
-struct DumpScratch {  // [ticket u32, pad u32][total u64][tile_off u64 x n_tiles][tile_cnt u32 x n_tiles]
-    uint32_t *ticket;
-    uint64_t *total, *tile_off;
-    uint32_t *tile_cnt;
-    DumpScratch(void *p, uint64_t n) {
-        const uint64_t n_tiles = (n + DUMP_TILE - 1) / DUMP_TILE;
-        ticket = (uint32_t *)p;
-        total = (uint64_t *)((char *)p + 8);
-        tile_off = (uint64_t *)((char *)p + 16);
-        tile_cnt = (uint32_t *)((char *)p + 16 + n_tiles * 8);
-    }
-};
 
 template <typename Src>
 int dump_measure(const Src &src, uint64_t n, uint32_t k, const DumpTables &T, void *scratch, uint64_t *total_host, hipStream_t s, unsigned max_blocks) {
-    const DumpScratch S(scratch, n);
-    PAG_HIP_TRY(hipMemsetAsync(scratch, 0, 16, s));
-    const unsigned grid = dump_grid(n, max_blocks);
-    if (T.in_lds) k_dump_measure<Src, true><<<dim3(grid), dim3(DUMP_TILE), 0, s>>>(src, n, k, T, S.tile_cnt, S.tile_off, S.ticket, S.total, total_host);
-    else k_dump_measure<Src, false><<<dim3(grid), dim3(DUMP_TILE), 0, s>>>(src, n, k, T, S.tile_cnt, S.tile_off, S.ticket, S.total, total_host);
-    PAG_HIP_TRY(hipGetLastError());
-    return PAG_OK;
+    const TextScratch S(scratch, n);
+    const int rc = text_scratch_reset(scratch, s);
+    if (rc) return rc;
+    return text_launch(T.in_lds ? k_dump_measure<Src, true> : k_dump_measure<Src, false>, n, max_blocks, s, src, n, k, T, S.tile_cnt, S.tile_off, S.ticket, S.total,
+                       total_host);
 }
 template <typename Src>
 int dump_render(const Src &src, uint64_t n, uint32_t k, const DumpTables &T, void *scratch, char *out, uint64_t cap, hipStream_t s, unsigned max_blocks) {
-    const DumpScratch S(scratch, n);
-    const unsigned grid = dump_grid(n, max_blocks);
-    if (T.in_lds) k_dump_render<Src, true><<<dim3(grid), dim3(DUMP_TILE), 0, s>>>(src, n, k, T, S.tile_off, S.total, (unsigned char *)out, cap);
-    else k_dump_render<Src, false><<<dim3(grid), dim3(DUMP_TILE), 0, s>>>(src, n, k, T, S.tile_off, S.total, (unsigned char *)out, cap);
-    PAG_HIP_TRY(hipGetLastError());
-    return PAG_OK;
+    const TextScratch S(scratch, n);
+    return text_launch(T.in_lds ? k_dump_render<Src, true> : k_dump_render<Src, false>, n, max_blocks, s, src, n, k, T, S.tile_off, S.total, (unsigned char *)out, cap);
 }
 
 uint32_t dec_digits(uint64_t v) {
@@ -299,7 +190,7 @@ uint32_t dec_digits(uint64_t v) {
 
 }  // namespace
 
-size_t dump_scratch_bytes(uint64_t n) { return (size_t)((16 + ((n + DUMP_TILE - 1) / DUMP_TILE) * 12 + 255) & ~(uint64_t)255); }
+size_t text_scratch_bytes(uint64_t n) { return TextScratch::bytes(n); }
 
 // PositionMapper's constructor (position_mapper.hpp:18-25) for both spaces, as u32: [cstart nc + 1][csize nc][rstart nr + 1][rsize nr]
 bool dump_tables_build(const uint32_t *ctg_len, uint64_t n_ctgs, const uint32_t *ref_len, uint64_t n_refs, std::vector<uint32_t> &blob) {
@@ -345,9 +236,9 @@ uint32_t dump_line_bound(uint32_t k, const std::vector<uint32_t> &blob, uint64_t
 }
 
 int trav_launch_dump_path(TravGraph G, const uint32_t *seq_v, const uint32_t *seq_s, uint64_t len, uint32_t k, const DumpTables &T, void *scratch,
-                          char *out, uint64_t cap, uint64_t *total_host, hipStream_t s, unsigned max_blocks) {
-    const DumpSrcPath src{G, seq_v, seq_s};
-    int rc = dump_measure(src, len, k, T, scratch, total_host, s, max_blocks);
+                          char *out, uint64_t cap, uint64_t *head_host, hipStream_t s, unsigned max_blocks) {
+    const PathSrcPath src{G, seq_v, seq_s};
+    int rc = dump_measure(src, len, k, T, scratch, head_host, s, max_blocks);
     return rc ? rc : dump_render(src, len, k, T, scratch, out, cap, s, max_blocks);
 }
 
@@ -369,41 +260,23 @@ extern "C" int pag_render_dump_lines(const pag_path_node *records, uint64_t n, u
     }
     if (!pag_device_available()) return PAG_ENODEV;  // (no CPU fallback)
     if (n == 0) return PAG_OK;
-    int caller_device = -1;
-    if (hipGetDevice(&caller_device) != hipSuccess) caller_device = -1, (void)hipGetLastError();
-    PAG_HIP_TRY(hipSetDevice(device));
-    struct Bufs {  // (a stream and the buffers of this one call; the caller's current device is put back at every exit)
-        void *rec = nullptr, *tab = nullptr, *scratch = nullptr, *text = nullptr;
-        hipStream_t s = nullptr;
-        int back = -1;
-        ~Bufs() {
-            hipFree(rec), hipFree(tab), hipFree(scratch), hipFree(text);
-            if (s) hipStreamDestroy(s);
-            if (back >= 0) (void)hipSetDevice(back);
-        }
-    } b;
-    b.back = caller_device == device ? -1 : caller_device;
-    PAG_HIP_TRY(hipStreamCreateWithFlags(&b.s, hipStreamNonBlocking));
-    PAG_HIP_TRY(hipMalloc(&b.rec, n * sizeof(pag_path_node)));
-    PAG_HIP_TRY(hipMalloc(&b.tab, blob.size() * 4 + 16));
-    PAG_HIP_TRY(hipMalloc(&b.scratch, dump_scratch_bytes(n)));
-    PAG_HIP_TRY(hipMemcpyAsync(b.rec, records, n * sizeof(pag_path_node), hipMemcpyHostToDevice, b.s));
-    if (!blob.empty()) PAG_HIP_TRY(hipMemcpyAsync(b.tab, blob.data(), blob.size() * 4, hipMemcpyHostToDevice, b.s));
+    TextCall b;
+    void *scratch = nullptr, *text = nullptr;
+    int rc = b.begin(device, n, blob);
+    if (rc || (rc = b.alloc(&scratch, text_scratch_bytes(n))) || (rc = b.upload(records, n, blob))) return rc;
     const DumpTables T = dump_tables_at((const uint32_t *)b.tab, n_ctgs, n_refs);
-    const DumpSrcRecords src{(const pag_path_node *)b.rec};
-    int rc = dump_measure(src, n, k, T, b.scratch, nullptr, b.s, 0);
-    if (rc) return rc;
+    const PathSrcRecords src{(const pag_path_node *)b.rec};
+    if ((rc = dump_measure(src, n, k, T, scratch, nullptr, b.s, 0))) return rc;
     uint64_t total = 0;
-    PAG_HIP_TRY(hipMemcpyAsync(&total, (char *)b.scratch + 8, 8, hipMemcpyDeviceToHost, b.s));
+    PAG_HIP_TRY(hipMemcpyAsync(&total, (char *)scratch + 8, 8, hipMemcpyDeviceToHost, b.s));
     PAG_HIP_TRY(hipStreamSynchronize(b.s));
     *bytes = total;
     if (total > cap) {
         set_error("pag_render_dump_lines: the text takes %llu bytes, the buffer holds %llu", (unsigned long long)total, (unsigned long long)cap);
         return PAG_ERANGE;
     }
-    PAG_HIP_TRY(hipMalloc(&b.text, total + 16));
-    if ((rc = dump_render(src, n, k, T, b.scratch, (char *)b.text, total, b.s, 0))) return rc;
-    PAG_HIP_TRY(hipMemcpyAsync(out, b.text, total, hipMemcpyDeviceToHost, b.s));
+    if ((rc = b.alloc(&text, total + 16)) || (rc = dump_render(src, n, k, T, scratch, (char *)text, total, b.s, 0))) return rc;
+    PAG_HIP_TRY(hipMemcpyAsync(out, text, total, hipMemcpyDeviceToHost, b.s));
     PAG_HIP_TRY(hipStreamSynchronize(b.s));
     return PAG_OK;
 }

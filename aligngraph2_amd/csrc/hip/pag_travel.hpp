@@ -251,10 +251,14 @@ struct TravConcatPart {
 void trav_launch_concat_parts(const TravConcatPart *parts, uint32_t n_parts, uint32_t *out_v, uint32_t *out_s, uint32_t first_step,
                               hipStream_t s);
 
-// ---- the text of a path dump (k5_dump.hip) ---------------------------------------------------------------------------
-// PositionMapper's tables of the contigs and of the references as the device reads them (u32: dump_tables_build refuses
-// coordinate spaces beyond 32 bits and more than DUMP_MAX_SEQS sequences, which also bounds a line's length); the starts of
-// both go to LDS when they have DUMP_LDS_STARTS entries or fewer.
+// ---- the texts of a path, rendered on the device (skeleton of both: text_tiles.hpp) -----------------------------------
+// Both launchers take a path as trav_launch_gather_path does (new ids + steps, max_blocks) and write into `out`, device or
+// pinned host memory (no alignment required), nothing at all when the text exceeds cap.  head_host (pinned, may be null)
+// receives the text's size in [0].
+size_t text_scratch_bytes(uint64_t n);  // device scratch of one rendering of a path of n vertices (256-byte multiple)
+// the dump's lines (k5_dump.hip).  PositionMapper's tables of the contigs and of the references as the device reads them
+// (u32: dump_tables_build refuses coordinate spaces beyond 32 bits and more than DUMP_MAX_SEQS sequences, which also bounds
+// a line's length); the starts of both go to LDS when they have DUMP_LDS_STARTS entries or fewer.
 constexpr uint32_t DUMP_LDS_STARTS = 5632u, DUMP_MAX_SEQS = 99999999u;
 struct DumpTables {
     const uint32_t *cstart, *csize, *rstart, *rsize;  // [nc + 1] [nc] [nr + 1] [nr]
@@ -294,16 +298,10 @@ __device__ __forceinline__ void single_to_dual(Starts starts, const uint32_t *__
 bool dump_tables_build(const uint32_t *ctg_len, uint64_t n_ctgs, const uint32_t *ref_len, uint64_t n_refs, std::vector<uint32_t> &blob);
 DumpTables dump_tables_at(const uint32_t *dev, uint64_t n_ctgs, uint64_t n_refs);
 uint32_t dump_line_bound(uint32_t k, const std::vector<uint32_t> &blob, uint64_t n_ctgs, uint64_t n_refs);
-size_t dump_scratch_bytes(uint64_t n);  // device scratch of one rendering of n lines (256-byte multiple)
-// the lines of a path (new ids + steps, as trav_launch_gather_path takes them) into `out` (device or pinned host memory, 16-byte
-// aligned buffer start not required); *total_host (pinned, may be null) receives the text's size — nothing is written when it
-// exceeds cap.  max_blocks as for trav_launch_gather_path.
 int trav_launch_dump_path(TravGraph G, const uint32_t *seq_v, const uint32_t *seq_s, uint64_t len, uint32_t k, const DumpTables &T, void *scratch,
-                          char *out, uint64_t cap, uint64_t *total_host, hipStream_t s, unsigned max_blocks);
+                          char *out, uint64_t cap, uint64_t *head_host, hipStream_t s, unsigned max_blocks);
 
-// ---- the consensus sequence of a path (k5_seq.hip) -------------------------------------------------------------------
-// PAlgorithm::seqToString from the records of a path: the bases of its steps, read out of the packed contigs and references
-// where a step is longer than k.  The packed sequences of both coordinate spaces on the device, one blob:
+// the consensus sequence, PAlgorithm::seqToString (k5_seq.hip).  The packed sequences of both coordinate spaces on the device, one blob:
 // [coff u64 x nc][roff u64 x nr][contigs' packed bytes, padded to 16][references' packed bytes]; the lengths are DumpTables'
 // csize / rsize.
 struct SeqSources {
@@ -319,10 +317,8 @@ struct SeqParams {
     uint64_t deviation;
     double error_rate;
 };
-size_t seq_scratch_bytes(uint64_t n);  // device scratch of one rendering of n vertices (256-byte multiple)
-// the sequence of a path (new ids + steps, as trav_launch_gather_path takes them) into `out` (device or pinned host memory).
-// head_host (pinned, may be null): [0] receives the text's size — nothing is written when it exceeds cap — and [1] becomes
-// non-zero when the path is not renderable (a rounded position negative or not finite: what `out` holds then means nothing).
+// head_host[1] becomes non-zero when the path is not renderable (a rounded position negative or not finite: what `out` holds
+// then means nothing).
 int trav_launch_seq_path(TravGraph G, const uint32_t *seq_v, const uint32_t *seq_s, uint64_t len, const SeqParams &P, const DumpTables &T,
                          const SeqSources &S, void *scratch, char *out, uint64_t cap, uint64_t *head_host, hipStream_t s, unsigned max_blocks);
 

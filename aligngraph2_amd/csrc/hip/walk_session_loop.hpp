@@ -858,36 +858,29 @@ struct WalkSession : WalkRounds {
                     if (cs.delivered || cs.travel.empty()) continue;
                     const size_t slot2 = 2 * (size_t)cs.ci + (cs.forward ? 0 : 1);
                     const uint32_t *ids = b_fin.as<uint32_t>() + g->path_off[slot2];
-                    if (render) {
-                        if ((rc = render_path(slot2, ids, ids + tot, cs.travel.size(), (char *)g->dump_scratch + sat, s, 0u))) return fail(rc);
-                        ++n_epilogue_texts;
-                        sat += dump_scratch_bytes(cs.travel.size());
-                    }
-                    if (render_seq) {
-                        if ((rc = render_seq_path(slot2, ids, ids + tot, cs.travel.size(), travel_bases(cs.travel, k), (char *)g->dump_scratch + sat, s, 0u))) return fail(rc);
-                        ++n_epilogue_seqs;
-                        sat += seq_scratch_bytes(cs.travel.size());
-                    }
+                    auto carve = [&](size_t bytes) {
+                        void *q = (char *)g->dump_scratch + sat;
+                        sat += bytes;
+                        return q;
+                    };
+                    const uint64_t bases = render_seq ? (uint64_t)k + positive_steps(cs.travel, 1, cs.travel.size()) : 0;
+                    if ((rc = render_texts(slot2, ids, ids + tot, cs.travel.size(), bases, carve, s, 0u))) return fail(rc);
+                    if (render) ++n_epilogue_texts;
+                    if (render_seq) ++n_epilogue_seqs;
                 }
             }
             PAG_HIP_TRY(hipStreamSynchronize(s));
             if (g->deliver_stream) PAG_HIP_TRY(hipStreamSynchronize(g->deliver_stream));  // (the deliveries made during the walks)
             resolve_texts();
-            if (timing && render) {
+            for (TextKind kind : {TEXT_DUMP, TEXT_SEQ}) {
+                const TextKindOf K = text_kind(kind);
+                if (!timing || !K.on) continue;
                 size_t n_text = 0, n_none = 0;
                 for (auto &cs : st) {
                     const size_t slot2 = 2 * (size_t)cs.ci + (cs.forward ? 0 : 1);
-                    if (g->path_len[slot2]) (g->text_ptr[slot2] ? n_text : n_none) += 1;
+                    if (g->path_len[slot2]) (K.ptr[slot2] ? n_text : n_none) += 1;
                 }
-                std::fprintf(stderr, "[timing] dump text: %zu contigs rendered (%zu of them in the epilogue), %zu left to the host\n", n_text, n_epilogue_texts, n_none);
-            }
-            if (timing && render_seq) {
-                size_t n_text = 0, n_none = 0;
-                for (auto &cs : st) {
-                    const size_t slot2 = 2 * (size_t)cs.ci + (cs.forward ? 0 : 1);
-                    if (g->path_len[slot2]) (g->seq_ptr[slot2] ? n_text : n_none) += 1;
-                }
-                std::fprintf(stderr, "[timing] sequence text: %zu paths rendered (%zu of them in the epilogue), %zu left to the host\n", n_text, n_epilogue_seqs, n_none);
+                std::fprintf(stderr, K.timing, n_text, K.n_epilogue, n_none);
             }
         }
         lap("epilogue");

@@ -325,7 +325,6 @@ struct WalkRounds : WalkJobs {
         std::fill(g->seq_ptr.begin(), g->seq_ptr.end(), nullptr);
         std::fill(g->seq_len.begin(), g->seq_len.end(), (uint64_t)0);
         text_pending.clear();
-        seq_pending.clear();
         return rc2;
     }
 
@@ -361,29 +360,40 @@ struct WalkRounds : WalkJobs {
     // (a delivery issued while walk jobs are live runs on 24 blocks: its thousands of waves, each with stores to host memory in
     // flight, slowed every walker wave beside them — 2.5 -> 3.2-5 us per classification in the last 40 ms of a block, round 5)
     static constexpr unsigned DELIVER_BLOCKS = 24;
-    // PAG_TRAVEL_RENDER_DUMPS: the dump text of every delivered path (k5_dump.hip) — from the same ids, on the same stream and
-    // under the same block cap as its gather, stored straight into pinned memory like the records.  The buffer is sized by a
-    // bound (dump_line_bound); the text's size arrives in front of it and is read when the stream has been waited for
-    // (resolve_texts): a text that did not fit was not written and the caller formats the records itself.
-    bool render = false;
+    // The texts of every delivered path (text_tiles.hpp) — from the same ids, on the same stream and under the same block cap as
+    // its gather, stored straight into pinned memory like the records.  A text's buffer is sized before the launch; its size
+    // as the device measured it arrives in front of it and is read when the stream has been waited for (resolve_texts): a text
+    // that did not fit was not written, and the caller renders that path itself.
+    // PAG_TRAVEL_RENDER_DUMPS: the dump's lines (k5_dump.hip), the buffer sized by a bound (dump_line_bound).
+    // PAG_TRAVEL_RENDER_SEQS: the consensus sequence (k5_seq.hip).  Its size is k + the positive steps, which this thread has (the
+    // tail of a path put together on the device: a bound from its chain's step sum); a path that is not renderable is the
+    // caller's too.  Needs the references' bases (pag_travel_seq_sources): without them nothing is rendered.
+    bool render = false, render_seq = false;
     DumpTables dump_tab{};
     uint32_t dump_bound = 0;
     std::vector<uint32_t> dump_blob;
+    SeqSources seq_src{};
+    enum TextKind { TEXT_DUMP, TEXT_SEQ };
     struct TextPending {
+        TextKind kind;
         size_t slot2;
-        char *buf;  // [u64 size, padding to 256][text]
+        char *buf;  // [u64 size][u64 not renderable, padding to 256][text]
         uint64_t cap;
     };
     std::vector<TextPending> text_pending;
-    size_t n_epilogue_texts = 0;
-    // PAG_TRAVEL_RENDER_SEQS: the consensus sequence of every delivered path (k5_seq.hip), the same way.  Its size is known
-    // before the launch — k + the positive steps, which this thread has (the tail of a path put together on the device: a bound
-    // from its chain's step sum) — and sizes the buffer; the device's own count and its "not renderable" flag arrive in front
-    // of the text (resolve_texts).  Needs the references' bases (pag_travel_seq_sources): without them nothing is rendered.
-    bool render_seq = false;
-    SeqSources seq_src{};
-    std::vector<TextPending> seq_pending;  // buf: [u64 size][u64 not renderable, padding to 256][text]
-    size_t n_epilogue_seqs = 0;
+    size_t n_epilogue_texts = 0, n_epilogue_seqs = 0;
+    struct TextKindOf {  // what tells the two kinds apart outside the launch itself
+        bool on;
+        std::vector<const char *> &ptr;  // the handle's slots for the text ...
+        std::vector<uint64_t> &len;      // ... and its size
+        size_t &n_epilogue;
+        const char *timing;              // its "[timing]" line
+    };
+    TextKindOf text_kind(TextKind kind) {
+        if (kind == TEXT_DUMP)
+            return {render, g->text_ptr, g->text_len, n_epilogue_texts, "[timing] dump text: %zu contigs rendered (%zu of them in the epilogue), %zu left to the host\n"};
+        return {render_seq, g->seq_ptr, g->seq_len, n_epilogue_seqs, "[timing] sequence text: %zu paths rendered (%zu of them in the epilogue), %zu left to the host\n"};
+    }
     int setup_render() {
         render = render_seq = false;
         const bool want_dumps = (prm->reserved & PAG_TRAVEL_RENDER_DUMPS) != 0;
@@ -412,53 +422,50 @@ struct WalkRounds : WalkJobs {
         }
         return PAG_OK;
     }
-    // bases: the text's size, or a bound of it
-    int render_seq_path(size_t slot2, const uint32_t *d_v, const uint32_t *d_s, size_t m, uint64_t bases, void *scratch, hipStream_t st, unsigned max_blocks) {
-        char *buf = (char *)fetch_alloc(256 + bases + 16);
-        if (!buf) return PAG_OK;  // (no pinned memory for the text, which is an extra: the caller renders that path itself)
-        ((uint64_t *)buf)[0] = ~0ull;
-        ((uint64_t *)buf)[1] = 0;
-        const SeqParams P{k, (uint64_t)deviation, errorRate};
-        int rc2 = trav_launch_seq_path(G, d_v, d_s, m, P, dump_tab, seq_src, scratch, buf + 256, bases, (uint64_t *)buf, st, max_blocks);
-        if (rc2 == PAG_OK) seq_pending.push_back(TextPending{slot2, buf, bases});
-        return rc2;
-    }
-    static uint64_t travel_bases(const std::vector<LNode> &seq, uint32_t k) {
-        uint64_t b = seq.empty() ? 0 : k;
-        for (size_t x = 1; x < seq.size(); ++x) b += seq[x].step > 0 ? (uint64_t)seq[x].step : 0ull;
+    // the positive steps of seq[from, to): a sequence is k bases + those behind its first vertex
+    static uint64_t positive_steps(const std::vector<LNode> &seq, size_t from, size_t to) {
+        uint64_t b = 0;
+        for (size_t x = from; x < to; ++x) b += seq[x].step > 0 ? (uint64_t)seq[x].step : 0ull;
         return b;
     }
-    size_t render_scratch_bytes(size_t m) const { return (render ? dump_scratch_bytes(m) : 0) + (render_seq ? seq_scratch_bytes(m) : 0); }
-    int render_path(size_t slot2, const uint32_t *d_v, const uint32_t *d_s, size_t m, void *scratch, hipStream_t st, unsigned max_blocks) {
-        const uint64_t cap = (uint64_t)m * dump_bound;
-        char *buf = (char *)fetch_alloc(256 + cap);
-        if (!buf) return PAG_OK;  // (no pinned memory for the text, which is an extra: the caller formats that contig's records itself)
-        *(uint64_t *)buf = ~0ull;
-        int rc2 = trav_launch_dump_path(G, d_v, d_s, m, k, dump_tab, scratch, buf + 256, cap, (uint64_t *)buf, st, max_blocks);
-        if (rc2 == PAG_OK) text_pending.push_back(TextPending{slot2, buf, cap});
-        return rc2;
-    }
+    size_t render_scratch_bytes(size_t m) const { return ((render ? 1 : 0) + (render_seq ? 1 : 0)) * text_scratch_bytes(m); }
     void *arena_scratch(size_t need) {  // (nullptr: no room — that contig's text is left to the caller)
         if (!g->walk_arena || g->walk_arena_used + need > g->walk_arena_cap) return nullptr;
         void *q = (char *)g->walk_arena + g->walk_arena_used;
         g->walk_arena_used += need;
         return q;
     }
+    // The texts that are switched on, of a delivered path of m vertices (d_v, d_s: its ids and steps on the device): the dump, then
+    // the sequence (bases: its size, or a bound of it; read only when sequences are rendered).  scratch(bytes): device scratch of
+    // one rendering, nullptr when there is none.  Without scratch or pinned memory a text — an extra — is not rendered, and the
+    // caller renders that path itself.  (The pinned buffer: header, text, 16 bytes to spare — for the dump too, which had none.)
+    template <typename Scratch>
+    int render_texts(size_t slot2, const uint32_t *d_v, const uint32_t *d_s, size_t m, uint64_t bases, Scratch scratch, hipStream_t st, unsigned max_blocks) {
+        for (TextKind kind : {TEXT_DUMP, TEXT_SEQ}) {
+            if (!text_kind(kind).on) continue;
+            void *sc = scratch(text_scratch_bytes(m));
+            const uint64_t cap = kind == TEXT_DUMP ? (uint64_t)m * dump_bound : bases;
+            char *buf = sc ? (char *)fetch_alloc(256 + cap + 16) : nullptr;
+            if (!buf) continue;
+            ((uint64_t *)buf)[0] = ~0ull;
+            ((uint64_t *)buf)[1] = 0;
+            const int rc2 = kind == TEXT_DUMP ? trav_launch_dump_path(G, d_v, d_s, m, k, dump_tab, sc, buf + 256, cap, (uint64_t *)buf, st, max_blocks)
+                                              : trav_launch_seq_path(G, d_v, d_s, m, SeqParams{k, (uint64_t)deviation, errorRate}, dump_tab, seq_src, sc, buf + 256, cap,
+                                                                     (uint64_t *)buf, st, max_blocks);
+            if (rc2) return rc2;
+            text_pending.push_back(TextPending{kind, slot2, buf, cap});
+        }
+        return PAG_OK;
+    }
     void resolve_texts() {  // (after the streams of all renderings have been waited for)
         for (const TextPending &t : text_pending) {
-            const uint64_t total = *(const volatile uint64_t *)t.buf;
-            if (total > t.cap) continue;
-            g->text_ptr[t.slot2] = t.buf + 256;
-            g->text_len[t.slot2] = total;
-        }
-        text_pending.clear();
-        for (const TextPending &t : seq_pending) {
             const uint64_t total = ((const volatile uint64_t *)t.buf)[0], bad = ((const volatile uint64_t *)t.buf)[1];
             if (total > t.cap || bad) continue;  // (did not fit its bound, or not renderable: the caller renders that path)
-            g->seq_ptr[t.slot2] = t.buf + 256;
-            g->seq_len[t.slot2] = total;
+            const TextKindOf K = text_kind(t.kind);
+            K.ptr[t.slot2] = t.buf + 256;
+            K.len[t.slot2] = total;
         }
-        seq_pending.clear();
+        text_pending.clear();
     }
     int deliver_contig(uint32_t i) {
         CtgState &cs = st[i];
@@ -486,19 +493,9 @@ struct WalkRounds : WalkJobs {
             }
             trav_launch_gather_path(G, T.d_ids, T.d_ids + T.cap, m, dst, g->deliver_stream, n_live ? DELIVER_BLOCKS : 0u);
             g->path_ptr[slot2] = dst;
-            if (render) {
-                void *scratch = arena_scratch(dump_scratch_bytes(m));
-                int rc2;
-                if (scratch && (rc2 = render_path(slot2, T.d_ids, T.d_ids + T.cap, m, scratch, g->deliver_stream, n_live ? DELIVER_BLOCKS : 0u))) return rc2;
-            }
-            if (render_seq) {
-                void *scratch = arena_scratch(seq_scratch_bytes(m));
-                uint64_t bases = (uint64_t)k + T.step_bound;  // (a bound: the first vertex counts k, a pumped last vertex nothing)
-                for (size_t x = 0; x < m0; ++x) bases += cs.travel[x].step > 0 ? (uint64_t)cs.travel[x].step : 0ull;
-                int rc2;
-                if (scratch && (rc2 = render_seq_path(slot2, T.d_ids, T.d_ids + T.cap, m, bases, scratch, g->deliver_stream, n_live ? DELIVER_BLOCKS : 0u))) return rc2;
-            }
-            return PAG_OK;
+            // (bases, a bound: the first vertex counts k, a pumped last vertex nothing)
+            return render_texts(slot2, T.d_ids, T.d_ids + T.cap, m, render_seq ? (uint64_t)k + T.step_bound + positive_steps(cs.travel, 0, m0) : 0,
+                                [&](size_t bytes) { return arena_scratch(bytes); }, g->deliver_stream, n_live ? DELIVER_BLOCKS : 0u);
         }
         if (cfg.debug_deliver_late) return PAG_OK;
         const size_t n = cs.travel.size();
@@ -528,18 +525,8 @@ struct WalkRounds : WalkJobs {
         PAG_HIP_TRY(hipMemcpyAsync(d_ids, hp, m * 8, hipMemcpyHostToDevice, g->deliver_stream));
         trav_launch_gather_path(G, d_ids, d_ids + m, m, dst, g->deliver_stream, n_live ? DELIVER_BLOCKS : 0u);
         g->path_ptr[slot2] = dst;
-        if (render) {
-            void *scratch = arena_scratch(dump_scratch_bytes(m));
-            int rc2;
-            if (scratch && (rc2 = render_path(slot2, d_ids, d_ids + m, m, scratch, g->deliver_stream, n_live ? DELIVER_BLOCKS : 0u))) return rc2;
-        }
-        if (render_seq) {
-            void *scratch = arena_scratch(seq_scratch_bytes(m));
-            int rc2;
-            if (scratch && (rc2 = render_seq_path(slot2, d_ids, d_ids + m, m, travel_bases(cs.travel, k), scratch, g->deliver_stream, n_live ? DELIVER_BLOCKS : 0u)))
-                return rc2;
-        }
-        return PAG_OK;
+        return render_texts(slot2, d_ids, d_ids + m, m, render_seq ? (uint64_t)k + positive_steps(cs.travel, 1, m) : 0, [&](size_t bytes) { return arena_scratch(bytes); },
+                            g->deliver_stream, n_live ? DELIVER_BLOCKS : 0u);
     }
 
     // ---- the event loop

@@ -399,6 +399,28 @@ def test_both_device_switches_together(name, workdir):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("name", ["join_fwd_t1", "three_ctg_multi_t4"])
+def test_both_device_switches_rendered_in_the_epilogue(name, workdir):
+    """both switches and PAG_DEBUG_DELIVER_LATE=1: the epilogue carves ONE scratch buffer for the dump and the sequence of every
+    contig, and renders both texts of every path behind its gather"""
+    out, err = run_case(name, workdir, "both_late", walk_env(PAGRAPH_DEVICE_SEQS="1", PAGRAPH_DEVICE_DUMPS="1", PAG_DEBUG_DELIVER_LATE="1"))
+    goldens.compare_out_dir(name, out)
+    for what in (r"dump text: (\d+) contigs", r"sequence text: (\d+) paths"):
+        n_text = n_epi = 0
+        for m in re.finditer(what + r" rendered \((\d+) of them in the epilogue\), (\d+) left to the host", err):
+            n_text += int(m.group(1))
+            n_epi += int(m.group(2))
+            assert int(m.group(3)) == 0
+        assert n_text > 0 and n_epi == n_text, err[-1500:]
+    all_from_the_device(name, workdir, err)  # (chain pieces: nothing host-rendered)
+    dumps = dump_text.golden_dumps(name)
+    m = [re.search(r"path dumps: device-rendered (\d+) bytes (\d+) vertices; host-rendered (\d+) contigs", ln) for ln in err.splitlines()]
+    m = [x for x in m if x]
+    assert sum(int(x.group(1)) for x in m) == sum(len(ln) for _, body in dumps.values() for ln in body)
+    assert sum(int(x.group(3)) for x in m) == 0
+
+
+@pytest.mark.gpu
 def test_device_seqs_switch_is_harmless_in_a_sharded_run(workdir):
     """PAGRAPH_SHARD: rank 0 builds the chains from the gathered paths of both ranks and renders their pieces on the host; the
     switch changes nothing there (set up as tests/test_gpu_cli.py::test_one_block_built_by_several_pagraph_processes)"""
