@@ -92,6 +92,8 @@ HOST_NOHIP_OBJS := $(filter-out $(B)/host/hip_backend.o $(B)/host/traverse_api.o
 HARNESS := tests/harness/bin/oracle_graph_dump tests/harness/bin/libpagh_test.so tests/harness/bin/pagraph_oracle \
            tests/harness/bin/seg_kernels_test tests/harness/bin/sort_bench tests/harness/bin/libpagh_walk_test.so \
            tests/harness/bin/libpagh_stitch_test.so
+# (built where its source is: a tree that carries another commit's tests/ still builds the rest of the harness)
+HARNESS += $(if $(wildcard tests/harness/round_test.cpp),tests/harness/bin/libpagh_round_test.so)
 harness: $(HARNESS)
 
 # kernel-level check of K3/K4 against a sequential restatement (needs a GPU to run)
@@ -138,6 +140,11 @@ tests/harness/bin/libpagh_walk_test.so: tests/harness/pagh_walk_test.cpp $(HOST_
 
 # the host bookkeeping of walks cut into pieces (walk_stitch.hpp: plain C++, no device code) for CPU unit tests
 tests/harness/bin/libpagh_stitch_test.so: tests/harness/stitch_test.cpp $(HIP_DIR)/walk_stitch.hpp
+	@mkdir -p tests/harness/bin
+	$(CXX) $(CXXFLAGS) -I$(HIP_DIR) -shared -o $@ $<
+
+# the per-round rules of a traversal (walk_round.hpp: plain C++ too) for CPU unit tests
+tests/harness/bin/libpagh_round_test.so: tests/harness/round_test.cpp $(HIP_DIR)/walk_round.hpp $(HIP_DIR)/walk_stitch.hpp include/pagraph_hip.h
 	@mkdir -p tests/harness/bin
 	$(CXX) $(CXXFLAGS) -I$(HIP_DIR) -shared -o $@ $<
 

@@ -6,7 +6,9 @@
 // after the first must reach minLen), splices the walk into the running path (appendSeq), records it in
 // the contig's global visited set (device hash set + host mirror), checks the repeat / leap stop rules
 // and prepares the next seeds (window scan on the device; ordering by edit distance with the same
-// unstable std::sort as the reference on the host).
+// unstable std::sort as the reference on the host).  Those rules are the plain functions of walk_round.hpp; the control
+// around them is WalkSession (walk_session_jobs.hpp, walk_session_rounds.hpp, walk_session_loop.hpp), the adoption
+// conditions of a walk cut into pieces walk_stitch.hpp, the traversal graph's preparation trav_prepare_host.hpp.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -23,10 +25,15 @@
 #include "pag_graph_impl.hpp"
 #include "pagraph_debug.h"
 #include "walk_config.hpp"
+#include "walk_round.hpp"
 #include "walk_stitch.hpp"
 #include "walker_grid.hpp"
 
 using namespace pagdev;
+using rounds::code2kmer;  // (walk_round.hpp: the per-round rules, and the helper types the preparation shares with them)
+using rounds::edit_distance;
+using rounds::LNode;
+using rounds::Mapper;
 
 namespace {
 
@@ -41,8 +48,8 @@ namespace {
 
 extern "C" {
 
-// test hooks (host code only, no device needed): the library's own copies of PositionMapper and editDistance against the
-// reference's function-level golden tables (tests/test_function_goldens.py)
+// test hooks (host code only, no device needed): the library's own copies of PositionMapper and editDistance (walk_round.hpp)
+// against the reference's function-level golden tables (tests/test_function_goldens.py)
 uint64_t pag_debug_edit_distance(const char *a, const char *b) { return edit_distance(a, b); }
 uint64_t pag_debug_mapper_d2s(const uint32_t *len, uint64_t n, int64_t idx, int64_t pos) { return Mapper(len, n).dualToSingle(idx, pos); }
 void pag_debug_mapper_s2d(const uint32_t *len, uint64_t n, uint64_t single, int64_t *idx, int64_t *pos) {

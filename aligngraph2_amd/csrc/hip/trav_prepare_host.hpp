@@ -1,89 +1,12 @@
-// The traversal graph of a handle, host side (included by k5_travel_host.hip, inside its anonymous namespace): the coordinate
-// mapper and small helpers of the per-round control, the view of a handle's traversals (trav_view_region) and trav_prepare_graph —
-// compact CSR, coordinate order, successor records (kernels: k5_view.hip, k5_succ.hip).
+// The traversal graph of a handle, host side (included by k5_travel_host.hip, inside its anonymous namespace, behind
+// walk_round.hpp): CtgState, the view of a handle's traversals (trav_view_region) and trav_prepare_graph — compact CSR,
+// coordinate order, successor records (kernels: k5_view.hip, k5_succ.hip).
 #pragma once
 
 double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-// PositionMapper (position/PositionMapper.cpp:16-64) over contig lengths
-struct Mapper {
-    std::vector<uint64_t> starts, sizes;
-    Mapper(const uint32_t *len, uint64_t n) {
-        for (uint64_t i = 0; i < n; ++i) sizes.push_back(len[i]);
-        if (sizes.empty()) return;
-        starts.push_back(sizes[0]);
-        for (size_t i = 1; i < sizes.size(); ++i) starts.push_back(starts.back() + 3 * sizes[i - 1] + std::max(sizes[i - 1], sizes[i]));
-        starts.push_back(starts.back() + 4 * sizes.back());
-    }
-    uint64_t dualToSingle(int64_t idx, int64_t pos) const {
-        if (idx == 0) return 0;
-        size_t i = (size_t)(idx > 0 ? idx - 1 : -idx - 1);
-        return starts[i] + (idx > 0 ? 0 : 2 * sizes[i]) + (uint64_t)pos;
-    }
-    std::pair<int64_t, int64_t> singleToDual(uint64_t single) const {
-        if (single == 0) return {0, 0};
-        auto it = std::upper_bound(starts.begin(), starts.end(), single);
-        if (it != starts.begin()) it = std::prev(it);
-        int64_t idx = it - starts.begin();
-        uint64_t off = single - *it;
-        uint64_t sz = (size_t)idx < sizes.size() ? sizes[(size_t)idx] : 0;
-        if (off >= 2 * sz) {
-            off -= 2 * sz;
-            idx = -(idx + 1);
-        } else {
-            ++idx;
-        }
-        return {idx, (int64_t)off};
-    }
-};
-
-std::string code2kmer(uint32_t code, uint32_t k) {
-    std::string s(k, 'A');
-    for (uint32_t i = 0; i < k; ++i) {
-        s[k - 1 - i] = "ACGT"[code & 3u];
-        code >>= 2;
-    }
-    return s;
-}
-
-// PAlgorithm::editDistance (PAlgorithm.cpp:46-69)
-size_t edit_distance(const std::string &a, const std::string &b) {
-    // (two rows of the table; on the stack for k-mer sized strings: this runs once per re-seed candidate)
-    size_t stack_rows[2][40];
-    std::vector<size_t> heap_rows;
-    size_t *dp[2] = {stack_rows[0], stack_rows[1]};
-    if (b.size() + 1 > 40) {
-        heap_rows.assign(2 * (b.size() + 1), 0);
-        dp[0] = heap_rows.data();
-        dp[1] = heap_rows.data() + b.size() + 1;
-    }
-    size_t flag = 0;
-    for (size_t j = 0; j <= b.size(); ++j) dp[flag][j] = j;
-    flag ^= 1;
-    for (size_t i = 1; i <= a.size(); ++i) {
-        for (size_t j = 0; j <= b.size(); ++j) {
-            if (j == 0) {
-                dp[flag][j] = i;
-            } else {
-                dp[flag][j] = std::min(dp[flag ^ 1][j] + 1, dp[flag][j - 1] + 1);
-                dp[flag][j] = std::min(dp[flag][j], dp[flag ^ 1][j - 1] + (a[i - 1] == b[j - 1] ? 0 : 1));
-            }
-        }
-        flag ^= 1;
-    }
-    return dp[flag ^ 1][b.size()];
-}
-
-// a vertex of a running travel sequence as the per-round control needs it: new id, step, contig coordinate.  The full
-// records (k-mer, reference coordinate, abundance) are gathered once, for the finished sequences.
-struct LNode {
-    uint32_t u;
-    int32_t step;
-    uint32_t ctg;
-    LNode() {}  // (left as it is by vector::resize: a round's path is written over the new elements right away, 14 M of them at configs[1])
-    LNode(uint32_t uu, int32_t st, uint32_t c) : u(uu), step(st), ctg(c) {}
-};
-
+// per (contig, orientation) that is walked: the state of its rounds (the rules that read and write it: walk_round.hpp) and
+// where its visited sets and its last walk lie on the device
 struct CtgState {
     size_t pendingFirst = 0;       // (choose + gather: the first vertex of the round's path in `travel`, and the step it gets)
     int32_t pendingFirstStep = 0;

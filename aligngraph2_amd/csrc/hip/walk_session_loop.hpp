@@ -338,10 +338,8 @@ struct WalkSession : WalkRounds {
         }
         {
             auto leaps = [&](uint32_t i) {  // the round ended on another contig: the contig is finished (PAlgorithm.cpp:254-262, 322-328)
-                for (const Chain &ch : RS[i].chains) {
-                    const uint32_t last_ctg = ch.len == 0 ? 0u : ch.parts.back().pc[ch.parts.back().n - 1];
-                    if (last_ctg != 0 && mapper.singleToDual(last_ctg).first != st[i].chosenOne) return true;
-                }
+                for (const Chain &ch : RS[i].chains)
+                    if (rounds::leaves_strand(mapper, rounds::end_coord(ch), st[i].chosenOne)) return true;
                 return false;
             };
             const size_t take = over_queue.size();
@@ -350,12 +348,9 @@ struct WalkSession : WalkRounds {
             over_queue.erase(over_queue.begin(), over_queue.begin() + (long)take);
         }
     }
-    // ---- per contig: choose (PAlgorithm.cpp:238-262); the chosen walks are uploaded, gathered and committed on the
+    // ---- per contig: choose (walk_round.hpp); the chosen walks are uploaded, gathered and committed on the
     //      device back to back, copied out, and spliced by a pool of host threads (contigs are independent)
-    struct Pick {
-        int chosen = -1;
-        bool leap = false;
-        size_t chooseCtgPos = 0, chooseRefPos = 0;
+    struct Pick : rounds::Choice {
         uint64_t off = 0, len = 0;
     };
     int take_walks(const std::vector<uint32_t> &batch, std::vector<Pick> &picks) {
@@ -367,21 +362,7 @@ struct WalkSession : WalkRounds {
                 RoundState &R = RS[i];
                 R.active = false;
                 Pick &P = picks[i];
-                size_t maxLen = 0;
-                for (size_t sd = 0; sd < R.chains.size(); ++sd) {
-                    const Chain &ch = R.chains[sd];
-                    const size_t len = ch.size;
-                    const uint32_t last_ctg = ch.len == 0 ? 0u : ch.parts.back().pc[ch.parts.back().n - 1];
-                    P.leap = last_ctg != 0 && mapper.singleToDual(last_ctg).first != cs.chosenOne;
-                    if (!P.leap && sd > 0 && prm->min_len > 0 && len < prm->min_len) continue;
-                    if (len > maxLen || P.leap) {
-                        maxLen = len;
-                        P.chosen = (int)sd;
-                        P.chooseCtgPos = (size_t)mapper.singleToDual(cs.seeds[sd].ctg).second;
-                        P.chooseRefPos = (size_t)refMapper.singleToDual(cs.seeds[sd].ref).second;
-                        if (P.leap) break;
-                    }
-                }
+                static_cast<rounds::Choice &>(P) = rounds::choose(R.chains, cs.seeds, mapper, refMapper, cs.chosenOne, prm->min_len);
                 if (P.chosen >= 0) {
                     P.len = R.chains[(size_t)P.chosen].len;
                     tot += P.len;  // (an upper bound: walks that stay on the device take no room, see below)
@@ -389,7 +370,7 @@ struct WalkSession : WalkRounds {
                 if (wtrace) trace.push_back(TraceEv{now_ms() - tw0, 2u, i, 0, P.chosen, R.round, P.leap ? 1u : 0u, P.chosen >= 0 ? R.chains[(size_t)P.chosen].len : 0, 0});
                 if (wdebug && P.chosen >= 0) {
                     const Chain &ch = R.chains[(size_t)P.chosen];
-                    const uint32_t last_ctg = ch.len == 0 ? 0u : ch.parts.back().pc[ch.parts.back().n - 1];
+                    const uint32_t last_ctg = rounds::end_coord(ch);
                     std::fprintf(stderr, "[walk] t=%.1f ms contig %u round %llu over: chain %d of %zu chosen, %llu vertices, size %llu, from offset %lld, ends at offset %lld (strand %u), mx %u%s\n",
                                  now_ms() - t_begin, i, (unsigned long long)R.round, P.chosen, R.chains.size(), (unsigned long long)ch.len, (unsigned long long)ch.size,
                                  (long long)cs.seeds[(size_t)P.chosen].ctg - (long long)cs.ctgLeft, last_ctg ? (long long)last_ctg - (long long)cs.ctgLeft : -1ll, cs.len,
@@ -402,7 +383,7 @@ struct WalkSession : WalkRounds {
             if (!hp) return fail(PAG_ENOMEM);
             if ((rc = b_gather.alloc(tot * 4 + 64))) return fail(rc);
             // ONE pass over the chosen walk of every contig of the batch (its parts lie where the fetches put them): the
-            // vertex ids for the device, the walk appended to the contig's running path (appendSeq, PAlgorithm.cpp:110-142),
+            // vertex ids for the device, the walk appended to the contig's running path (appendSeq: walk_round.hpp trim_path),
             // the coordinate window of the global table, the vertices outside the strand's id range.  (Five passes and two
             // copies of the walk before: 14 M path vertices per block at configs[1], on the thread every contig waits for.)
             // The chosen chains' parts are copied to the contigs' paths (cs.travel) and to the id list of the commit in chunks,
@@ -426,15 +407,9 @@ struct WalkSession : WalkRounds {
                 const Chain &ch = RS[i].chains[(size_t)P.chosen];
                 CtgState &cs = st[i];
                 std::vector<LNode> &base = cs.travel;
-                int64_t dLen = 0;
-                const uint32_t head_ctg = ch.parts.front().pc[0];
-                int32_t dist = (int32_t)k;
-                while (!base.empty() && (base.back().ctg == 0 || head_ctg <= base.back().ctg)) {
-                    dLen -= base.back().step;
-                    base.pop_back();
-                }
-                if (!base.empty()) dist = (int32_t)(head_ctg - base.back().ctg);
-                const size_t at0 = base.size();
+                const rounds::Trim trim = rounds::trim_path(base, ch.parts.front().pc[0], k);
+                const size_t at0 = trim.at0;
+                const int32_t dist = trim.dist;
                 if (P.leap && !RS[i].slot_bufs && g->walk_arena && !cfg.debug_deliver_late) {
                     // the contig is finished by this walk (splice below): nothing of it is needed on the host
                     bool on_dev = true;
@@ -449,7 +424,7 @@ struct WalkSession : WalkRounds {
                         T.cap = cap;
                         T.m0 = at0;
                         T.n = P.len;
-                        T.last_ctg = ch.parts.back().pc[ch.parts.back().n - 1];
+                        T.last_ctg = rounds::end_coord(ch);
                         T.step_bound = ch.size + (uint64_t)(dist > 0 ? dist : 0);  // (the chain's steps, its first one replaced by dist.  A bound of the POSITIVE steps because no step of a walk is negative:
                         // they are the successor records' steps, an unsigned 24-bit field of SuccRec::meta.  Were one ever negative the text
                         // would exceed its buffer, nothing would be written and the host would render that path)
@@ -467,14 +442,13 @@ struct WalkSession : WalkRounds {
                 for (const Chain::Part &pt : ch.parts)
                     for (size_t x0 = 0; x0 < pt.n; x0 += CHUNK)
                         chunks.push_back(CopyChunk{i, &pt, x0, std::min(pt.n, x0 + CHUNK), dst + pt.start, ids + pt.start, {}});
-                dLen += (int64_t)ch.size;
                 if (ch.low_nz != 0xFFFFFFFFu) {  // (some vertex has a coordinate)
                     cs.gwinLo = std::min(cs.gwinLo, ch.low_nz);
                     cs.gwinHi = std::max(cs.gwinHi, ch.mx_all);
                 }
                 cs.gFreeHi = std::max(cs.gFreeHi, ch.m0_all);
                 // the first vertex of the round's path: its step is the distance to the path so far (set after the copy)
-                cs.varLen += dLen - ((int64_t)ch.parts.front().s[0] - dist);
+                cs.varLen += rounds::var_len_gain(trim, ch.size, ch.parts.front().s[0]);
                 cs.pendingFirst = at0;
                 cs.pendingFirstStep = dist;
             }
@@ -531,62 +505,32 @@ struct WalkSession : WalkRounds {
         lap("choose+gather");
         return PAG_OK;
     }
-    // splice + stop rules (PAlgorithm.cpp:264-360); reqs / req_cs: the seed searches of the contigs that go on
+    // stop rules and the next round's anchor (walk_round.hpp); reqs / req_cs: the seed searches of the contigs that go on
     void splice_batch(const std::vector<uint32_t> &batch, const std::vector<Pick> &picks, std::vector<TravSeedReq> &reqs, std::vector<uint32_t> &req_cs) {
         std::vector<TravSeedReq> slot_req(n_sel);
         std::vector<uint8_t> slot_has(n_sel, 0);
         auto splice = [&](uint32_t i) {
             CtgState &cs = st[i];
             const Pick &P = picks[i];
-            const bool leap = P.leap;
-            // (the walk was appended to cs.travel by take_walk above)
-            if (P.chooseCtgPos != 0) {
-                cs.ctgQ.push_back((uint32_t)P.chooseCtgPos);
-                while (cs.ctgQ.size() > 4) cs.ctgQ.pop_front();
-            }
-            if (P.chooseRefPos != 0) {
-                cs.refQ.push_back((uint32_t)P.chooseRefPos);
-                while (cs.refQ.size() > 4) cs.refQ.pop_front();
-            }
-            bool ctgRepeat = false, refRepeat = false;
-            if (cs.ctgQ.size() >= 4) {
-                auto mm = std::minmax_element(cs.ctgQ.begin(), cs.ctgQ.end());
-                ctgRepeat = (uint64_t)(*mm.second - *mm.first) <= 2 * deviation;
-            }
-            if (cs.refQ.size() >= 4) {
-                auto mm = std::minmax_element(cs.refQ.begin(), cs.refQ.end());
-                refRepeat = (uint64_t)(*mm.second - *mm.first) <= 2 * deviation;
-            }
-            if (ctgRepeat || refRepeat || leap) {
-                if (leap) cs.finalLeap = true;
+            // (the walk was appended to cs.travel by take_walks above)
+            const rounds::Stop stop = rounds::stop_rules(cs.ctgQ, cs.refQ, P, deviation);
+            if (stop.done) {
+                if (stop.finalLeap) cs.finalLeap = true;
                 cs.done = true;
                 return;
             }
-            // last contig-consistent vertex of the running path (PAlgorithm.cpp:332-360)
-            uint64_t lastCtgPos = 0;
-            uint32_t lastU = 0;  // (its k-mer is looked up on the device together with the next seeds)
-            bool haveKmer = false;
-            for (auto it = cs.travel.rbegin(); it != cs.travel.rend(); ++it) {
-                if (it->ctg != 0) {
-                    auto d = mapper.singleToDual(it->ctg);
-                    if (d.first == cs.chosenOne && d.second >= 0) {
-                        lastCtgPos = (uint64_t)d.second;
-                        lastU = it->u;
-                        haveKmer = true;
-                        break;
-                    }
-                }
-            }
+            const rounds::Anchor an = rounds::last_on_strand(cs.travel, mapper, cs.chosenOne);  // (its k-mer is looked up on the device together with the next seeds)
+            const rounds::Window w = rounds::seed_window(an.pos, deviation);
             TravSeedReq r{};
             r.ctg = i;
-            r.pos = lastCtgPos;
-            r.left = lastCtgPos - std::min<uint64_t>(lastCtgPos, 1000 * deviation);
-            r.right = lastCtgPos + 1000 * deviation;
+            r.pos = an.pos;
+            r.left = w.left;
+            r.right = w.right;
             slot_req[i] = r;
             slot_has[i] = 1;
             cs.seeds.clear();
-            cs.parentU = lastU;
-            cs.haveParent = haveKmer;
+            cs.parentU = an.u;
+            cs.haveParent = an.found;
         };
         {
             unsigned nthr = std::min<unsigned>((unsigned)batch.size(), std::max(1u, std::min(32u, std::thread::hardware_concurrency())));
@@ -650,20 +594,8 @@ struct WalkSession : WalkRounds {
             }
             std::vector<uint32_t> vids;
             std::vector<size_t> cnt(reqs.size());
-            for (size_t q = 0; q < reqs.size(); ++q) {
-                std::unordered_set<uint32_t> seen;
-                size_t n = 0;
-                for (uint32_t part = 0; part < PARTS; ++part) {  // (the parts of the window, in offset order)
-                    const uint32_t *o = &wb[(q * PARTS + part) * WSTRIDE];
-                    for (uint32_t x = 0; x < o[0]; ++x) {
-                        uint32_t v = o[1 + x];
-                        if (!seen.insert(v).second) continue;         // std::set `unique` in searchPANode2
-                        vids.push_back(v);                            // (filterPANodes was applied by the kernel)
-                        ++n;
-                    }
-                }
-                cnt[q] = n;
-            }
+            for (size_t q = 0; q < reqs.size(); ++q)  // (filterPANodes was applied by the kernel)
+                cnt[q] = rounds::window_candidates(&wb[q * PARTS * WSTRIDE], PARTS, WSTRIDE, vids);
             std::vector<pag_path_node> attrs;
             if ((rc = fetch_vertices(vids, attrs))) return fail(rc);
             {   // k-mers of the parents (last contig-consistent vertex of each running path)
@@ -685,20 +617,8 @@ struct WalkSession : WalkRounds {
             for (size_t q = 0; q < reqs.size(); ++q) {
                 CtgState &cs = st[req_cs[q]];
                 const std::string parent = cs.haveParent ? code2kmer(cs.parentCode, k) : std::string();
-                std::vector<pag_path_node> cand(attrs.begin() + at, attrs.begin() + at + cnt[q]);
+                rounds::order_seeds(attrs.data() + at, cnt[q], parent, k, topK, cs.seeds);
                 at += cnt[q];
-                // std::sort with the reference's comparator (edit distance to the parent k-mer), unstable:
-                // precomputed keys give the same comparison outcomes, hence the same permutation
-                struct Keyed {
-                    size_t d;
-                    pag_path_node n;
-                };
-                std::vector<Keyed> keyed;
-                keyed.reserve(cand.size());
-                for (auto &c : cand) keyed.push_back({edit_distance(parent, code2kmer(c.code, k)), c});
-                std::sort(keyed.begin(), keyed.end(), [](const Keyed &a, const Keyed &b) { return a.d < b.d; });
-                cs.seeds.clear();
-                for (size_t x = 0; x < keyed.size() && x < topK; ++x) cs.seeds.push_back(keyed[x].n);
                 if (cs.seeds.empty()) {
                     cs.done = true;
                     give_up_segments(req_cs[q]);
@@ -804,7 +724,7 @@ struct WalkSession : WalkRounds {
 
         // ---- epilogue: whatever has not been delivered while the walks ran (see deliver_contig)
         for (uint32_t i = 0; i < n_sel; ++i)
-            if (!st[i].delivered) filter_travel(st[i]);
+            if (!st[i].delivered) rounds::filter_travel(st[i].travel, st[i].finalLeap, mapper, st[i].ci, startSplit);
         {   // the full records of those sequences: one gather, results straight into the pinned array the handle keeps for
             // pag_travel_path()
             uint64_t tot = 0;

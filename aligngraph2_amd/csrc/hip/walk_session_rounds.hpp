@@ -328,31 +328,6 @@ struct WalkRounds : WalkJobs {
         return rc2;
     }
 
-    // filterSequence / "Pump it" of a finished contig (PAlgorithm.cpp:409-423)
-    bool pumped(const CtgState &cs, uint32_t last_ctg) {  // the last vertex of a path that ends in a leap is dropped?
-        auto d = mapper.singleToDual(last_ctg);
-        uint64_t a = (uint64_t)std::llabs(d.first);
-        return a == (uint64_t)cs.ci + 1 || (a >= 1 && a <= mapper.sizes.size() && (double)d.second >= (double)mapper.sizes[a - 1] * (1 - startSplit));
-    }
-    void filter_travel(CtgState &cs) {
-        auto &seq = cs.travel;
-        if (!cs.finalLeap) {
-            const size_t windowSize = 10;
-            if (seq.size() >= windowSize) {
-                size_t startIdx = seq.size() - seq.size() / 90;
-                for (size_t i = startIdx; i < seq.size() - windowSize + 1; ++i) {
-                    uint32_t firstPos = seq[i].ctg;
-                    uint32_t secondPos = seq[std::min(seq.size(), i + windowSize) - 1].ctg;
-                    if (secondPos != 0 && firstPos != 0 && secondPos < firstPos) {
-                        seq.resize(i + 1);
-                        break;
-                    }
-                }
-            }
-        } else if (!seq.empty()) {
-            if (pumped(cs, seq.back().ctg)) seq.pop_back();
-        }
-    }
     // A contig whose traversal is over is DELIVERED while the others still walk: its sequence is filtered, the full records of
     // its vertices are gathered on the device and copied (asynchronously, stream s) into pinned memory that lives until the
     // next call — at configs[1] the one gather + 380 MB copy for all contigs used to follow the last walk (15 ms).
@@ -472,7 +447,7 @@ struct WalkRounds : WalkJobs {
         if (cs.delivered || !cs.done) return PAG_OK;
         if (cs.tail.on) {  // (a path that ends in a leap: finalLeap, nothing but the last vertex to filter)
             const CtgState::DevTail &T = cs.tail;
-            const size_t m0 = T.m0, m = m0 + T.n - (pumped(cs, T.last_ctg) ? 1 : 0);
+            const size_t m0 = T.m0, m = m0 + T.n - (rounds::pumped(mapper, T.last_ctg, cs.ci, startSplit) ? 1 : 0);
             const size_t slot2 = 2 * (size_t)cs.ci + (cs.forward ? 0 : 1);
             cs.delivered = true;
             g->path_off[slot2] = 0;
@@ -501,7 +476,7 @@ struct WalkRounds : WalkJobs {
         const size_t n = cs.travel.size();
         const size_t need = ((n * 8 + 255) & ~(size_t)255) + 512 + render_scratch_bytes(n);
         if (!g->walk_arena || g->walk_arena_used + need > g->walk_arena_cap) return PAG_OK;
-        filter_travel(cs);
+        rounds::filter_travel(cs.travel, cs.finalLeap, mapper, cs.ci, startSplit);
         const size_t m = cs.travel.size();
         const size_t slot2 = 2 * (size_t)cs.ci + (cs.forward ? 0 : 1);
         cs.delivered = true;

@@ -2,8 +2,8 @@
 tests/golden/func_mapper.txt, func_edit.txt) against the product's own copies of those functions:
 
   PositionMapper (position/PositionMapper.cpp:16-64)   csrc/host/position_mapper.hpp  (graph input, writers)
-                                                       Mapper in csrc/hip/k5_travel_host.hip (traversal control)
-  PAlgorithm::editDistance (PAlgorithm.cpp:46-69)      edit_distance in csrc/hip/k5_travel_host.hip (seed ordering)
+                                                       Mapper in csrc/hip/walk_round.hpp (traversal control)
+  PAlgorithm::editDistance (PAlgorithm.cpp:46-69)      edit_distance in csrc/hip/walk_round.hpp (seed ordering)
 
 The hooks are plain host functions; no GPU is needed to call them."""
 import ctypes as C
