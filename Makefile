@@ -94,6 +94,7 @@ HARNESS := tests/harness/bin/oracle_graph_dump tests/harness/bin/libpagh_test.so
            tests/harness/bin/libpagh_stitch_test.so
 # (built where its source is: a tree that carries another commit's tests/ still builds the rest of the harness)
 HARNESS += $(if $(wildcard tests/harness/round_test.cpp),tests/harness/bin/libpagh_round_test.so)
+HARNESS += $(if $(wildcard tests/harness/serial_layout_test.cpp),tests/harness/bin/libpagh_serial_layout_test.so)
 harness: $(HARNESS)
 
 # kernel-level check of K3/K4 against a sequential restatement (needs a GPU to run)
@@ -147,6 +148,16 @@ tests/harness/bin/libpagh_stitch_test.so: tests/harness/stitch_test.cpp $(HIP_DI
 tests/harness/bin/libpagh_round_test.so: tests/harness/round_test.cpp $(HIP_DIR)/walk_round.hpp $(HIP_DIR)/walk_stitch.hpp include/pagraph_hip.h
 	@mkdir -p tests/harness/bin
 	$(CXX) $(CXXFLAGS) -I$(HIP_DIR) -shared -o $@ $<
+
+# where one owner's records land in a serial-rank run (serial_layout.hpp: plain C++) for CPU unit tests, and the same cases as a
+# program of its own under the address and undefined-behaviour sanitizers (host code only; built and run by tests/test_serial_layout.py)
+tests/harness/bin/libpagh_serial_layout_test.so: tests/harness/serial_layout_test.cpp $(HIP_DIR)/serial_layout.hpp
+	@mkdir -p tests/harness/bin
+	$(CXX) $(CXXFLAGS) -I$(HIP_DIR) -shared -o $@ $<
+
+tests/harness/bin/serial_layout_sanitized: tests/harness/serial_layout_main.cpp $(HIP_DIR)/serial_layout.hpp
+	@mkdir -p tests/harness/bin
+	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=all -I$(HIP_DIR) -o $@ $<
 
 clean:
 	rm -rf $(B) aligngraph2_amd/libpagraph_hip.so aligngraph2_amd/bin tests/harness/bin

@@ -109,6 +109,12 @@ class Region(C.Structure):
     _fields_ = [("n_ctg_iv", _u64), ("ctg_iv", _vp), ("n_ref_iv", _u64), ("ref_iv", _vp), ("ref_open", _vp)]
 
 
+class SerialStats(C.Structure):
+    _c_name_ = "pag_serial_stats"
+    _fields_ = [("held_vertices", _u64), ("held_edges", _u64), ("tuples_in", _u64), ("edges_in", _u64), ("region_bytes", _u64),
+                ("s_extract", _f64), ("s_build", _f64), ("s_select", _f64), ("s_import", _f64)]
+
+
 class TravelParams(C.Structure):
     _c_name_ = "pag_travel_params"
     _fields_ = [("ref_threads", _u32), ("reserved", _u32), ("deviation", _u64), ("error_rate", _f64), ("start_split", _f64),
@@ -151,7 +157,7 @@ class TraverseStats(C.Structure):
 
 
 STRUCTS = {s._c_name_: s for s in (PagSeqs, PagAlnDb, PagBuildInput, PagRawDb, PagRawInput, BuildStats, Csr, ShardSlice, Region,
-                                   TravelParams, TravelStats, PagSucc, CnsAln, CnsPart, KmerCountResult, TraverseStats)}
+                                   SerialStats, TravelParams, TravelStats, PagSucc, CnsAln, CnsPart, KmerCountResult, TraverseStats)}
 
 # structs of the two headers that are deliberately mirrored neither in STRUCTS nor in DTYPES: C name -> why.  (The opaque
 # handles pag_graph and pag_comm have no body to mirror.)
@@ -176,6 +182,7 @@ SIGNATURES = {
     "pag_prepare": (_int, [_vp, _vp, _vp]),
     "pag_shard_extract": (_int, [_vp, _vp, _u32, _u32, _u64p]),
     "pag_shard_extract_range": (_int, [_vp, _vp, _u64, _u64, _u32, _u64p]),
+    "pag_shard_extract_for": (_int, [_vp, _vp, _u64, _u64, _u32, _u32, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _u64, _u64, _u64, _u64p]),
     "pag_shard_take": (_int, [_vp, _vp, _vp, _vp, _vp]),
     "pag_shard_take_part": (_int, [_vp, _u64, _u64, _vp, _vp, _u64, _u64, _vp, _vp]),
     "pag_shard_build": (_int, [_vp, _vp, _vp, _u64, _u64, _vp, _vp, _u64, _u64, _u32, _stats]),
@@ -197,6 +204,7 @@ SIGNATURES = {
     "pag_comm_gather_v": (_int, [_vp, _vp, _u64, _int, _vp, _u64, _vp, _vp]),
     "pag_comm_all_to_all_v": (_int, [_vp, _vp, _vp, _vp, _vp]),
     "pag_shard_run": (_int, [_vp, _vp, _vp, _vp, _stats]),
+    "pag_shard_run_serial": (_int, [_vp, _vp, _vp, _u32, _u32, _stats, _vp]),
     "pag_csr_sizes": (_int, [_vp, _u64p, _u64p, _u64p]),
     "pag_export_csr": (_int, [_vp, _vp]),
     "pag_travel_prepare": (_int, [_vp, _vp, _vp, _u64, _vp, _vp]),
@@ -245,6 +253,8 @@ SIGNATURES = {
     "pag_debug_cov_filter": (_int, [_vp, _u64, _vp, _u64, _u32, _vp, _int]),
     "pag_debug_predicates": (_int, [_vp, _u64, _f64, _vp, _vp, _int]),
     "pag_debug_predicates_tab": (_int, [_vp, _u64, _f64, _vp, _vp, _int, _vp]),
+    "pag_debug_owner_pick": (_int, [_vp, _vp, _u64, _u64, _u32, _u32, _vp, _vp, _u64, _u64, _u64, _u64p, _int]),
+    "pag_debug_shard_run_serial": (_int, [_vp, _vp, _vp, _u32, _u32, _stats, _vp, _int]),
     "pagh_debug_classify_columns": (None, [_cs, _u64, _cs, _u64, _vp, _vp, _vp, _int]),
     "pagh_debug_pack_bases": (None, [_cs, _u64, _vp, _int]),
 }

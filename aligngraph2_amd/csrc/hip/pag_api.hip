@@ -790,6 +790,39 @@ int pag_shard_extract_range(pag_graph *g, const pag_build_input *in, uint64_t lo
     return PAG_OK;
 }
 
+// pag_shard_extract_range + pag_shard_take_part of ONE owner's two stretches, without the partition in between: the streams
+// stay as extract_stage left them and the owner's records are compacted straight to where the caller wants them
+// (k_owner_pick.hip).  No ping-pong partner and no sort scratch is allocated on this path.
+int pag_shard_extract_for(pag_graph *g, const pag_build_input *in, uint64_t lo, uint64_t hi, uint32_t n_shards, uint32_t owner, uint32_t *tkey,
+                          uint64_t *tval, uint64_t t_cap, uint64_t t_at1, uint64_t t_at2, uint32_t *ekey, uint64_t *eval, uint64_t e_cap,
+                          uint64_t e_at1, uint64_t e_at2, uint64_t *counts) {
+    int rc = check_process_args(g, in);
+    if (rc != PAG_OK) return rc;
+    const int lg = log2_shards(n_shards);
+    if (lg < 1 || owner >= n_shards || !counts || 2 * (int)g->k < lg || lo > hi || hi > in->reads.n_seqs) {
+        set_error("pag_shard_extract_for: n_shards must be 2, 4 or 8 (got %u) and the owner below it (got %u), the reads [%llu, %llu) of %llu", n_shards,
+                  owner, (unsigned long long)lo, (unsigned long long)hi, (unsigned long long)in->reads.n_seqs);
+        return PAG_EINVAL;
+    }
+    PAG_HIP_TRY(hipSetDevice(g->device));
+    free_graph_results(g);
+    hipStream_t s = g->stream;
+    Extracted x;
+    if ((rc = extract_stage(g, in, lo, hi, &x, nullptr, nullptr))) return rc;
+    g->shard_x[0] = x.T;
+    g->shard_x[1] = x.E;
+    g->shard_in0[0] = g->shard_in0[1] = 1;
+    for (int q = 0; q < 4; ++q) counts[q] = 0;
+    const uint32_t shift = (uint32_t)(2 * (int)g->k - lg);
+    DevBuf b_tmp(g, ps::PICK_TMP);
+    if ((rc = b_tmp.alloc(owner_pick_tmp_bytes(std::max(x.T, x.E))))) return rc;
+    const StreamPtrs st = streams_at(g, 1, 1);
+    if ((rc = owner_pick(st.tkey, st.tval, x.T, x.T1, shift, owner, tkey, tval, t_cap, t_at1, t_at2, counts, b_tmp.p, s))) return rc;
+    if ((rc = owner_pick(st.ekey, st.eval, x.E, x.E1, shift, owner, ekey, eval, e_cap, e_at1, e_at2, counts + 2, b_tmp.p, s))) return rc;
+    PAG_HIP_TRY(hipStreamSynchronize(s));
+    return PAG_OK;
+}
+
 int pag_shard_take(pag_graph *g, uint32_t *tkey, uint64_t *tval, uint32_t *ekey, uint64_t *eval) {
     if (!g) return PAG_EINVAL;
     PAG_HIP_TRY(hipSetDevice(g->device));
@@ -1041,3 +1074,36 @@ int pag_debug_streams(const pag_graph *g, uint32_t *tkey, uint64_t *tval, uint32
 }
 
 }  // extern "C"
+
+int pagdev::shard_count_range(pag_graph *g, const pag_build_input *in, uint64_t lo, uint64_t hi, uint32_t n_shards, uint64_t *counts) {
+    int rc = check_process_args(g, in);
+    if (rc != PAG_OK) return rc;
+    const int lg = log2_shards(n_shards);
+    if (lg < 1 || !counts || 2 * (int)g->k < lg || lo > hi || hi > in->reads.n_seqs) return PAG_EINVAL;
+    PAG_HIP_TRY(hipSetDevice(g->device));
+    free_graph_results(g);
+    hipStream_t s = g->stream;
+    Extracted x;
+    if ((rc = extract_stage(g, in, lo, hi, &x, nullptr, nullptr))) return rc;
+    g->shard_x[0] = x.T;
+    g->shard_x[1] = x.E;
+    g->shard_in0[0] = g->shard_in0[1] = 1;
+    DevBuf b_ctr(g, ps::CTR);
+    if ((rc = b_ctr.alloc(512))) return rc;
+    unsigned long long *ctr = b_ctr.as<unsigned long long>();
+    const StreamPtrs st = streams_at(g, 1, 1);
+    const int shift = 2 * (int)g->k - lg;
+    PAG_HIP_TRY(hipMemsetAsync(ctr, 0, 256, s));
+    if (x.T) owner_counts<<<dim3(1024), dim3(256), 0, s>>>(st.tkey, x.T, x.T1, shift, ctr);
+    if (x.E) owner_counts<<<dim3(1024), dim3(256), 0, s>>>(st.ekey, x.E, x.E1, shift, ctr + 16);
+    unsigned long long h[32];
+    PAG_HIP_TRY(hipMemcpyAsync(h, ctr, 256, hipMemcpyDeviceToHost, s));
+    PAG_HIP_TRY(hipStreamSynchronize(s));
+    for (uint32_t o = 0; o < n_shards; ++o) {
+        counts[4 * o + 0] = h[2 * o];
+        counts[4 * o + 1] = h[2 * o + 1];
+        counts[4 * o + 2] = h[16 + 2 * o];
+        counts[4 * o + 3] = h[16 + 2 * o + 1];
+    }
+    return PAG_OK;
+}

@@ -134,6 +134,14 @@ size_t sort_tmp_bytes(uint64_t n);
 int sort_pairs(uint32_t *k0, uint64_t *v0, uint32_t *k1, uint64_t *v1, uint64_t n, int key_bits, void *tmp,
                int *result_in_0, hipStream_t s, float *ms_dominant_kernel, int *n_passes, int first_bit = 0);
 
+// stable compaction of ONE owner's records out of a stream in emission order (k_owner_pick.hip): the records i of (key, val)[n]
+// with (key[i] >> shift) == owner, in stream order — those with i < n1 (pass 1) to (okey, oval)[at1 ..), the others to [at2 ..).
+// counts[0 / 1] = how many of each.  Nothing is written unless both stretches end inside the cap records of the destination
+// (PAG_ERANGE then, the counts are still reported).  tmp: owner_pick_tmp_bytes(n).  Waits for the stream once (the counts).
+size_t owner_pick_tmp_bytes(uint64_t n);
+int owner_pick(const uint32_t *key, const uint64_t *val, uint64_t n, uint64_t n1, uint32_t shift, uint32_t owner, uint32_t *okey,
+               uint64_t *oval, uint64_t cap, uint64_t at1, uint64_t at2, uint64_t *counts, void *tmp, hipStream_t s);
+
 struct ExtractArgs {
     // reads
     const uint64_t *read_off;

@@ -29,6 +29,14 @@ struct pag_graph {
     // ping-pong pair holds them
     uint64_t shard_x[2] = {0, 0};
     int shard_in0[2] = {1, 1};
+    // a serial-rank run (pag_shard_run_serial, shard_serial.hip): what turn 0 found — counts[(r * n + o) * 4 + q], the records
+    // read range r sends owner o, and the block's count lines — held against every later turn of the block
+    struct SerialRun {
+        bool valid = false;
+        uint32_t n = 0;
+        std::vector<uint64_t> counts;
+        pag_build_stats total{};
+    } serial;
     // device memory pool: every buffer of the pipeline lives in a named slot (the registry: pool_slots.hpp) that is reused
     // (and only ever grown) across pag_process calls, so steady-state calls do no hipMalloc/hipFree at all
     struct Slot {
@@ -157,6 +165,11 @@ inline StreamPtrs streams_at(const pag_graph *g, int t_in0, int e_in0) {
     return StreamPtrs{(const uint32_t *)g->pool[t_in0 ? ps::TK0 : ps::TK1].p, (const uint64_t *)g->pool[t_in0 ? ps::TV0 : ps::TV1].p,
                       (const uint32_t *)g->pool[e_in0 ? ps::EK0 : ps::EK1].p, (const uint64_t *)g->pool[e_in0 ? ps::EV0 : ps::EV1].p};
 }
+
+// Both extraction passes for the reads [lo, hi) of the emission order and the records per (owner, pass) of the two streams
+// (pag_api.hip): pag_shard_extract_range without its partition — the streams stay as extract_stage left them, no ping-pong
+// partner and no sort scratch is touched.  counts[o * 4 + q] as pag_shard_extract has them.
+int shard_count_range(pag_graph *g, const pag_build_input *in, uint64_t lo, uint64_t hi, uint32_t n_shards, uint64_t *counts);
 
 // the seven arrays of a graph (the handle's, a pag_shard_slice's) in the order of ps::GraphArr: read out, pointed elsewhere
 struct GraphArrays {

@@ -133,12 +133,15 @@ enum Id : int {
     SEND,                                   // family GraphArr: the selections of all destinations, one behind the other
     SEND_LAST = SEND + GRAPH_ARRS - 1,
 
+    // ---- one owner's records out of an extraction (pag_shard_extract_for, k_owner_pick.hip): tile counters, their scans, scan scratch
+    PICK_TMP,
+
     COUNT
 };
 
 constexpr Id family(Id base, int i) { return (Id)((int)base + i); }
 constexpr Id prep_db(int db, PrepDbBuf b) { return family(PREP_DB, db * PREP_DB_BUFS + b); }  // database db's copy of a PrepDbBuf
-static_assert(PREP_DB_LAST + 1 == IN_ROFF && IMPORT_LAST + 1 == TG_NCODE && SEL_OUT_LAST + 1 == OWN_TK && SEND_LAST + 1 == COUNT,
+static_assert(PREP_DB_LAST + 1 == IN_ROFF && IMPORT_LAST + 1 == TG_NCODE && SEL_OUT_LAST + 1 == OWN_TK && SEND_LAST + 1 == PICK_TMP,
               "a family's members lie between its base and the next entry");
 
 // pag_shard_release_build hands back everything but the imported graph and the traversal's (graph and session) slots

@@ -21,6 +21,10 @@ per-rank device footprint of every stage measured (hipMemGetInfo around the stag
 It is not how a multi-GPU node runs the block (that is `pag_shard_run` / `bin/pagraph` under PAGRAPH_SHARD), and no
 multi-GPU timing follows from it.
 
+`run` is that measuring aid and the reference the native schedule is checked against; `run_native` drives the same schedule where
+the product has it: pag_shard_run_serial (one handle, csrc/hip/shard_serial.hip) + pag_travel, turn by turn — what bin/pagraph does
+under PAGRAPH_SERIAL_RANKS.
+
 Reference semantics: the block is one `PositionProcessor::process` + one `PAssembly::testTravel5` (pagraph.cpp:181-263,
 PAssembly.cpp:30-79); the partition argument for bit-identity is the sharded build's (include/pagraph_hip.h, pag_shard_*).
 """
@@ -287,6 +291,133 @@ def run(hip, host, make_handle, inp, *, n_ranks, eps, k, threads, ctgs, ctg_alns
     # ---- rank 0's part: the chains of the whole block from the gathered travel sequences ---------------------------------
     t0 = time.perf_counter()
 
+    ts = TraverseStats()
+    orient_arr = np.array(list(orient), dtype=np.int32)
+    rc = host.pagh_assemble_paths(None, k, C.byref(ctg_seqs), None, C.byref(ref_seqs), None, orient_arr.ctypes.data, paths, lens, threads, eps, min_len,
+                                  out_dir.encode(), b"0_", 0, C.byref(ts))
+    if rc != 0:
+        raise RuntimeError(f"pagh_assemble_paths failed ({rc}): {host.pagh_last_error().decode()}")
+    res["s_assemble"] = time.perf_counter() - t0
+    res["outputs_sha256"], res["outputs_bytes"] = digest_dir(out_dir)
+    res.update(path_nodes=int(ts.n_path_nodes), path_bases=int(ts.n_path_bases), path_checksum=f"{ts.path_checksum:016x}",
+               chains=int(ts.n_chains_emitted), s_total=time.perf_counter() - t_all)
+    return res
+
+
+class _PeakSampler:
+    """the highest device usage seen while a library call runs (the call builds and releases inside itself: before and after
+    do not show its peak); sampled from a thread, every `period` seconds"""
+
+    def __init__(self, torch, device, period=0.02):
+        import threading
+        self.peak = _used(torch, device)
+        self._stop = threading.Event()
+
+        def loop():
+            while not self._stop.wait(period):
+                self.peak = max(self.peak, _used(torch, device))
+
+        self._th = threading.Thread(target=loop, daemon=True)
+        self._th.start()
+
+    def stop(self):
+        self._stop.set()
+        self._th.join()
+        return self.peak
+
+
+def run_native(hip, host, make_handle, inp, *, n_ranks, eps, k, threads, ctgs, ctg_alns, ref_lens, ctg_seqs, ref_seqs, orient, out_dir,
+               device="cuda", halo=200_000, min_len=50, log=None, via_partition=False):
+    """`run` with the schedule in the library: pag_shard_run_serial + pag_travel turn by turn on ONE handle (make_handle() is called
+    once), then pagh_assemble_paths.  Arguments as `run` takes them; via_partition (test and measurement only): the owners'
+    records through pag_shard_extract_range + pag_shard_take_part instead of pag_shard_extract_for (pag_debug_shard_run_serial).
+    Returns the keys of `run` that exist here: count lines, per-rank held_vertices / held_edges / held_fraction and stage
+    seconds, device peak (sampled), times, output digest, path statistics."""
+    import torch
+    say = log or (lambda *a: None)
+    capi.bind(hip)
+    capi.bind(host)
+    if os.path.isdir(out_dir) and os.listdir(out_dir):
+        raise ValueError(f"rank_serial: {out_dir} exists and is not empty (nothing of the caller's is ever removed)")
+    os.makedirs(out_dir, exist_ok=True)
+    N = n_ranks
+    n_ctg = len(ctgs)
+    first_aln = {}
+    for (c, ri, tb, te) in ctg_alns:
+        first_aln.setdefault(c, (ri, tb))
+    rst = parallel.mapper_starts(ref_lens)
+    ref_begin = [rst[first_aln[c][0]] + first_aln[c][1] if c in first_aln else 0 for c in range(n_ctg)]
+    deal = parallel.deal_contigs(list(ctgs), N, ref_begin=ref_begin)
+    regions = parallel.regions_for(deal, list(ctgs), orient, ctg_alns, list(ref_lens), halo=halo)
+    region_arr = (capi.Region * N)(*[d["region"] for d in regions])
+    res = {"n_ranks": N, "halo": halo, "schedule": "pag_shard_run_serial: destination-major on one handle, everything a rank takes in recomputed on the device",
+           "ranks": [dict() for _ in range(N)], "contigs_per_rank": [len(d) for d in deal], "via_partition": bool(via_partition)}
+    t_all = time.perf_counter()
+    host0 = _host_bytes()
+    torch.cuda.empty_cache()
+    base = _used(torch, device)
+    res["device_bytes_inputs_and_caller"] = base
+    sampler = _PeakSampler(torch, device)
+    g = make_handle()
+    prm = TravelParams(threads, 0, 2 * eps, 0.15, 0.90, min_len)
+    ref_len_arr = np.array(list(ref_lens), dtype=np.uint32)
+    paths = (C.c_void_p * (2 * n_ctg))()
+    lens = (C.c_uint64 * (2 * n_ctg))()
+    keep = []
+    count_lines = None
+    n_pos_total = 0
+    try:
+        for d in range(N):
+            info = res["ranks"][d]
+            t0 = time.perf_counter()
+            tot, st = capi.BuildStats(), capi.SerialStats()
+            if via_partition:
+                rc = hip.pag_debug_shard_run_serial(C.c_void_p(g), C.byref(inp), region_arr, N, d, C.byref(tot), C.byref(st), 1)
+            else:
+                rc = hip.pag_shard_run_serial(C.c_void_p(g), C.byref(inp), region_arr, N, d, C.byref(tot), C.byref(st))
+            if rc != 0:
+                raise RuntimeError(f"rank {d}: pag_shard_run_serial failed ({rc}): {hip.pag_last_error().decode()}")
+            t1 = time.perf_counter()
+            if count_lines is None:
+                count_lines = [int(x) for x in tot.counts()]
+                n_pos_total = int(tot.total_pos[1] - tot.merge_pos[1])  # (the block's vertices: what pass 2 leaves, summed over the owners)
+            elif count_lines != [int(x) for x in tot.counts()]:
+                raise RuntimeError(f"rank {d}: count lines {list(tot.counts())} differ from those of rank 0's turn {count_lines}")
+            info.update(held_vertices=int(st.held_vertices), held_edges=int(st.held_edges), held_fraction=st.held_vertices / max(1, n_pos_total),
+                        tuples_in=int(st.tuples_in), edges_in=int(st.edges_in), wire_in_region_bytes=int(st.region_bytes),
+                        s_recompute_extract=st.s_extract, s_recompute_build=st.s_build, s_recompute_select=st.s_select, s_import=st.s_import,
+                        s_build_turn=t1 - t0, bytes_region_imported=_used(torch, device) - base)
+            mine = np.full(n_ctg, -1, dtype=np.int32)
+            for cidx in deal[d]:
+                mine[cidx] = orient[cidx]
+            n_nodes_path = 0
+            if len(deal[d]):
+                rc = hip.pag_travel(C.c_void_p(g), C.byref(ctg_seqs), mine.ctypes.data, ref_len_arr.ctypes.data, len(ref_len_arr), C.byref(prm), None)
+                if rc != 0:
+                    raise RuntimeError(f"rank {d}: pag_travel failed ({rc}): {hip.pag_last_error().decode()}")
+                torch.cuda.synchronize(device)
+                info["bytes_traversal_peak"] = _used(torch, device) - base
+                for cidx in deal[d]:
+                    for fwd in ((1, 0) if mine[cidx] == 2 else ((1,) if mine[cidx] == 1 else (0,))):
+                        n = C.c_uint64()
+                        p = hip.pag_travel_path_oriented(C.c_void_p(g), cidx, fwd, C.byref(n))
+                        buf = C.create_string_buffer(C.string_at(p, n.value * 24), n.value * 24) if n.value else None  # (a path lives until the next pag_travel)
+                        keep.append(buf)
+                        slot = 2 * cidx + (0 if fwd else 1)
+                        paths[slot] = C.cast(buf, C.c_void_p).value if buf is not None else None
+                        lens[slot] = n.value
+                        n_nodes_path += n.value
+            info.update(s_travel=time.perf_counter() - t1, s_turn=time.perf_counter() - t0, path_nodes=int(n_nodes_path), contigs=len(deal[d]))
+            say(f"rank {d}: its region built in {t1 - t0:.1f} s (extract {st.s_extract:.1f}, build {st.s_build:.1f}, select {st.s_select:.1f}, import "
+                f"{st.s_import:.1f}); holds {info['held_fraction']:.3f} of the vertices, {len(deal[d])} contigs walked in {info['s_travel']:.1f} s")
+    finally:
+        res["device_bytes_peak_of_the_serial_run"] = sampler.stop()
+        host.pagh_release(C.c_void_p(g))
+        hip.pag_destroy(C.c_void_p(g))
+    res["count_lines_sum_over_owners"] = count_lines
+    res["vertices_total"] = n_pos_total
+    res["host_bytes_growth"] = max(0, _host_bytes() - host0)
+    t0 = time.perf_counter()
     ts = TraverseStats()
     orient_arr = np.array(list(orient), dtype=np.int32)
     rc = host.pagh_assemble_paths(None, k, C.byref(ctg_seqs), None, C.byref(ref_seqs), None, orient_arr.ctypes.data, paths, lens, threads, eps, min_len,

@@ -35,6 +35,16 @@ int pag_debug_cov_filter(const pag_aln *aln, uint64_t n_aln, const pag_ref *refs
 int pag_debug_predicates(const uint32_t *rows, uint64_t n, double err, uint8_t *grade, uint8_t *edge_sim, int device);
 int pag_debug_predicates_tab(const uint32_t *rows, uint64_t n, double err, uint8_t *grade, uint8_t *edge_sim, int device,
                              uint64_t *n_through_table);
+/* the stable compaction of one owner's records (k_owner_pick.hip) on HOST arrays: the records i of (key, val)[n] with
+ * (key[i] >> shift) == owner, in order — i < n1 to out[at1 ..), the others to out[at2 ..); counts[2].  out_key / out_val[cap]
+ * are uploaded as they are and come back: what the kernel did not write is what the caller put there. */
+int pag_debug_owner_pick(const uint32_t *key, const uint64_t *val, uint64_t n, uint64_t n1, uint32_t shift, uint32_t owner,
+                         uint32_t *out_key, uint64_t *out_val, uint64_t cap, uint64_t at1, uint64_t at2, uint64_t *counts, int device);
+/* pag_shard_run_serial with the owner's records taken the other way when via_partition != 0: pag_shard_extract_range (both
+ * streams partitioned by owner) + pag_shard_take_part.  For the one measurement that compares the two, and the test that
+ * they build the same graph. */
+int pag_debug_shard_run_serial(pag_graph *g, const pag_build_input *in, const pag_region *regions, uint32_t n_ranks, uint32_t turn,
+                               pag_build_stats *total, pag_serial_stats *st, int via_partition);
 
 /* ---- libpagraph_host.so ---- */
 /* one record's column classes / one sequence packed, by the production path or by the scalar loop alone */

@@ -259,6 +259,15 @@ int pag_shard_extract(pag_graph *g, const pag_build_input *in, uint32_t shard, u
  * chunks and sends chunk c to the owners while chunk c + 1 is extracted (SURVEY.md 8e "overlap with extraction by chunking"); the
  * chunks of a shard, one behind the other, are the shard's range, so the owner's layout argument above holds chunk by chunk. */
 int pag_shard_extract_range(pag_graph *g, const pag_build_input *in, uint64_t emit_lo, uint64_t emit_hi, uint32_t n_shards, uint64_t *counts);
+/* pag_shard_extract_range followed by pag_shard_take_part of ONE owner's two stretches, without partitioning the streams: the
+ * records of `owner` among the reads [emit_lo, emit_hi), in stream order, compacted straight into caller (device) buffers —
+ * its pass-1 tuples to tkey / tval[t_at1 ..), its pass-2 tuples to [t_at2 ..), edges likewise; t_cap / e_cap: records the
+ * buffers hold (PAG_ERANGE, nothing written, when a stretch would end beyond it).  counts[4] = {tuples pass 1, tuples pass 2,
+ * edges pass 1, edges pass 2} written.  n_shards = 2, 4 or 8.  For a caller that gathers one owner's records from several
+ * extractions (pag_shard_run_serial): no ping-pong partner and no sort scratch is allocated on this path. */
+int pag_shard_extract_for(pag_graph *g, const pag_build_input *in, uint64_t emit_lo, uint64_t emit_hi, uint32_t n_shards, uint32_t owner,
+                          uint32_t *tkey, uint64_t *tval, uint64_t t_cap, uint64_t t_at1, uint64_t t_at2, uint32_t *ekey, uint64_t *eval,
+                          uint64_t e_cap, uint64_t e_at1, uint64_t e_at2, uint64_t *counts);
 int pag_shard_take(pag_graph *g, uint32_t *tkey, uint64_t *tval, uint32_t *ekey, uint64_t *eval);
 int pag_shard_take_part(pag_graph *g, uint64_t t_off, uint64_t t_n, uint32_t *tkey, uint64_t *tval, uint64_t e_off, uint64_t e_n, uint32_t *ekey,
                         uint64_t *eval);
@@ -325,6 +334,26 @@ int pag_comm_all_to_all_v(pag_comm *c, const void *send_dev, const uint64_t *sen
  * ranks: pag_shard_select) sent to it and received straight into the handle's graph; the handle then holds what THIS
  * rank's traversals need (pag_shard_set_region done, the build's memory released).  total: the block's count lines. */
 int pag_shard_run(pag_graph *g, pag_comm *c, const pag_build_input *in, const pag_region *regions, pag_build_stats *total);
+
+/* ---- a block larger than one GPU's memory on ONE GPU: the ranks of a sharded build, one after the other ----------------
+ * The block as n_ranks ranks taking turns on ONE device and ONE handle: builds what rank `turn` of a PAGRAPH_SHARD run would
+ * hold after pag_shard_run - for every owner o (ascending): owner o's records from every read range (range r = emission
+ * positions [r * n / N, (r + 1) * n / N); canonical order, see the pag_shard_* comment; pag_shard_extract_for), K2-K4,
+ * pag_shard_select for regions[turn], appended to the handle's graph in owner order - then the region is set and the build's
+ * memory released (the arrays of a device-resident `in` stay: the next turn reads them again).  Nothing is parked in host
+ * memory: what a rank would receive is recomputed when its turn comes.  total = the block's count lines (sums over the
+ * owners; the same in every turn).  The caller then runs pag_travel for the contigs of that rank, copies their paths, and
+ * calls again with turn + 1 ON THE SAME HANDLE; turn 0 begins a block.  Checked in every turn: the records a read range sends
+ * an owner are those turn 0 counted, the count lines are those of turn 0 (PAG_EFAULT with a message otherwise).  A failure
+ * of any stage returns its code and leaves the handle destroyable; there are no retries.  n_ranks = 2, 4 or 8. */
+typedef struct pag_serial_stats {      /* what THIS turn did; every field measured, none estimated */
+    uint64_t held_vertices, held_edges;        /* pag_csr_sizes after the import */
+    uint64_t tuples_in, edges_in;              /* records the owners received for this turn, summed */
+    uint64_t region_bytes;                     /* bytes of the selections imported */
+    double s_extract, s_build, s_select, s_import;
+} pag_serial_stats;
+int pag_shard_run_serial(pag_graph *g, const pag_build_input *in, const pag_region *regions, uint32_t n_ranks, uint32_t turn,
+                         pag_build_stats *total, pag_serial_stats *st);
 
 /* sizes of the finished graph, then the graph itself into caller buffers */
 int pag_csr_sizes(const pag_graph *g, uint64_t *n_nodes, uint64_t *n_pos, uint64_t *n_edges);
