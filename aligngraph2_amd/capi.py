@@ -255,6 +255,10 @@ SIGNATURES = {
     "pag_debug_predicates_tab": (_int, [_vp, _u64, _f64, _vp, _vp, _int, _vp]),
     "pag_debug_owner_pick": (_int, [_vp, _vp, _u64, _u64, _u32, _u32, _vp, _vp, _u64, _u64, _u64, _u64p, _int]),
     "pag_debug_shard_run_serial": (_int, [_vp, _vp, _vp, _u32, _u32, _stats, _vp, _int]),
+    "pag_debug_zone_bands": (_int, [_vp, _u64, _vp, _u32, _vp, _vp, _int]),
+    "pag_debug_trav_compact": (_int, [_u32, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _region, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      _vp, _int]),
+    "pag_debug_view_region": (_int, [_vp, _vp, _u64, _vp, _vp, _u64, _f64, _vp, _vp, _vp, _vp, _u64]),
     "pagh_debug_classify_columns": (None, [_cs, _u64, _cs, _u64, _vp, _vp, _vp, _int]),
     "pagh_debug_pack_bases": (None, [_cs, _u64, _vp, _int]),
 }

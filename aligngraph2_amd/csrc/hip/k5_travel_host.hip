@@ -131,6 +131,32 @@ int pag_debug_trav_vertices(const pag_graph *g, uint32_t *code, uint64_t *pos) {
     return PAG_OK;
 }
 
+// ... and what trav_view_region makes of the handle's current graph for the traversals `orient` names (the tables
+// pag_travel_prepare_for would cut the view with), see pagraph_debug.h
+int pag_debug_view_region(pag_graph *g, const uint32_t *ctg_len, uint64_t n_ctgs, const int32_t *orient, const uint32_t *ref_len, uint64_t n_refs,
+                          double start_split, uint32_t *civ, uint32_t *riv, uint8_t *ropen, uint64_t *sizes, uint64_t cap) {
+    if (!g || !orient || !sizes || (n_ctgs && !ctg_len) || (n_refs && !ref_len) || (cap && (!civ || !riv || !ropen))) return PAG_EINVAL;
+    if (!g->tval && g->n_t) return PAG_EINVAL;
+    PAG_HIP_TRY(hipSetDevice(g->device));
+    ViewRegion vr;
+    int rc;
+    {
+        DevBuf b_view(g, ps::TG_VIEW);
+        if ((rc = trav_view_region(g, WalkConfig::from_env(), ctg_len, n_ctgs, orient, ref_len, n_refs, start_split, b_view, &vr))) return rc;
+    }
+    sizes[0] = vr.civ.size() / 2;
+    sizes[1] = vr.riv.size() / 2;
+    if (sizes[0] > cap || sizes[1] > cap) {
+        set_error("pag_debug_view_region: %llu contig intervals and %llu reference bands, room for %llu", (unsigned long long)sizes[0], (unsigned long long)sizes[1],
+                  (unsigned long long)cap);
+        return PAG_ERANGE;
+    }
+    std::copy(vr.civ.begin(), vr.civ.end(), civ);
+    std::copy(vr.riv.begin(), vr.riv.end(), riv);
+    std::copy(vr.ropen.begin(), vr.ropen.end(), ropen);
+    return PAG_OK;
+}
+
 // PABruijnGraph::successors for one vertex of the prepared view (PABruijnGraph.cpp:370-373 -> searchSuccessors :167-197), see pagraph_hip.h
 int64_t pag_successors(const pag_graph *g, uint32_t code, uint64_t pos, pag_succ *out, uint64_t cap) {
     if (!g || !g->tg_ready || (!out && cap)) return PAG_EINVAL;

@@ -5,11 +5,13 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
 #include "pag_device.hpp"
 #include "pag_travel.hpp"
+#include "pagraph_debug.h"
 #include "trav_device.hpp"
 
 namespace pagdev {
@@ -620,3 +622,154 @@ int trav_order(TravGraph G, uint32_t *key, uint64_t *val, uint32_t *key2, uint64
 }
 
 }  // namespace pagdev
+
+using namespace pagdev;
+
+// test hooks (include/pagraph_debug.h): the zone bands and the compaction on caller-given HOST arrays, with device buffers of
+// their own (the manner of pag_debug_owner_pick, k_owner_pick.hip)
+extern "C" int pag_debug_zone_bands(const uint64_t *tval, uint64_t T, const uint32_t *zones, uint32_t n_z, uint32_t *lo, uint32_t *hi, int device) {
+    if ((T && !tval) || (n_z && (!zones || !lo || !hi))) return PAG_EINVAL;
+    int before = 0;
+    PAG_HIP_TRY(hipGetDevice(&before));
+    PAG_HIP_TRY(hipSetDevice(device));
+    void *d_val = nullptr, *d_z = nullptr, *d_lo = nullptr, *d_hi = nullptr;
+    hipStream_t s = nullptr;
+    auto run = [&]() -> int {
+        PAG_HIP_TRY(hipStreamCreate(&s));
+        PAG_HIP_TRY(hipMalloc(&d_val, T * 8 + 16));
+        PAG_HIP_TRY(hipMalloc(&d_z, (size_t)n_z * 8 + 16));
+        PAG_HIP_TRY(hipMalloc(&d_lo, (size_t)n_z * 4 + 16));
+        PAG_HIP_TRY(hipMalloc(&d_hi, (size_t)n_z * 4 + 16));
+        if (T) PAG_HIP_TRY(hipMemcpyAsync(d_val, tval, T * 8, hipMemcpyHostToDevice, s));
+        if (n_z) PAG_HIP_TRY(hipMemcpyAsync(d_z, zones, (size_t)n_z * 8, hipMemcpyHostToDevice, s));
+        const int r = trav_zone_bands((const uint64_t *)d_val, T, (const uint32_t *)d_z, n_z, (uint32_t *)d_lo, (uint32_t *)d_hi, s);
+        if (r != PAG_OK) return r;
+        if (n_z) PAG_HIP_TRY(hipMemcpyAsync(lo, d_lo, (size_t)n_z * 4, hipMemcpyDeviceToHost, s));
+        if (n_z) PAG_HIP_TRY(hipMemcpyAsync(hi, d_hi, (size_t)n_z * 4, hipMemcpyDeviceToHost, s));
+        PAG_HIP_TRY(hipStreamSynchronize(s));
+        return PAG_OK;
+    };
+    const int rc = run();
+    if (s) hipStreamSynchronize(s);
+    for (void *p : {d_val, d_z, d_lo, d_hi})
+        if (p) hipFree(p);
+    if (s) hipStreamDestroy(s);
+    hipSetDevice(before);
+    return rc;
+}
+
+extern "C" int pag_debug_trav_compact(uint32_t k, const uint32_t *tkey, const uint64_t *tval, const uint32_t *tseg, const uint16_t *tcnt, uint64_t T,
+                                      const uint32_t *ekey, const uint64_t *eval, const uint32_t *eseg, uint64_t E, const pag_region *region,
+                                      uint64_t *vpos, uint16_t *vcnt, uint32_t *vnode, uint32_t *ncode, uint32_t *npos_off, uint32_t *nedge_off,
+                                      uint32_t *eto, uint32_t *estep, uint64_t *counts, int device) {
+    if (!counts || k < 1 || k > 16 || (T && (!tkey || !tval || !tseg || !tcnt)) || (E && (!ekey || !eval || !eseg)) || !npos_off || !nedge_off)
+        return PAG_EINVAL;
+    if (region && ((region->n_ctg_iv && !region->ctg_iv) || (region->n_ref_iv && !region->ref_iv))) return PAG_EINVAL;
+    const uint64_t nn = counts[0], np = counts[1], ne = counts[2];
+    if (nn > T || np > T || ne > E || T >= 0xFFFFFFF0ull || E >= 0xFFFFFFF0ull) return PAG_EINVAL;
+    if ((np && (!vpos || !vcnt || !vnode)) || (nn && !ncode) || (ne && (!eto || !estep))) return PAG_EINVAL;
+    int before = 0;
+    PAG_HIP_TRY(hipGetDevice(&before));
+    PAG_HIP_TRY(hipSetDevice(device));
+    const uint64_t n_words = ((1ull << (2 * k)) + 63) / 64;
+    const size_t tmp_bytes = trav_compact_tmp_bytes(T, E, k, nn);
+    const uint64_t n_civ = region ? region->n_ctg_iv : 0, n_riv = region ? region->n_ref_iv : 0;
+    void *d_tkey = nullptr, *d_tval = nullptr, *d_tseg = nullptr, *d_tcnt = nullptr, *d_ekey = nullptr, *d_eval = nullptr, *d_eseg = nullptr, *d_iv = nullptr,
+         *d_vpos = nullptr, *d_vcnt = nullptr, *d_vnode = nullptr, *d_ncode = nullptr, *d_npos = nullptr, *d_nedge = nullptr, *d_eto = nullptr, *d_estep = nullptr,
+         *d_bitmap = nullptr, *d_rank = nullptr, *d_tmp = nullptr;
+    hipStream_t s = nullptr;
+    auto run = [&]() -> int {
+        PAG_HIP_TRY(hipStreamCreate(&s));
+        PAG_HIP_TRY(hipMalloc(&d_tkey, T * 4 + 16));
+        PAG_HIP_TRY(hipMalloc(&d_tval, T * 8 + 16));
+        PAG_HIP_TRY(hipMalloc(&d_tseg, T * 4 + 16));
+        PAG_HIP_TRY(hipMalloc(&d_tcnt, T * 2 + 16));
+        PAG_HIP_TRY(hipMalloc(&d_ekey, E * 4 + 16));
+        PAG_HIP_TRY(hipMalloc(&d_eval, E * 8 + 16));
+        PAG_HIP_TRY(hipMalloc(&d_eseg, E * 4 + 16));
+        PAG_HIP_TRY(hipMalloc(&d_iv, (n_civ + n_riv + 4) * 8));
+        // (the sizes trav_prepare_graph gives the arrays of the traversal graph; the node arrays with room for a node per vertex:
+        // a slot wrongly taken for the first of its segment is then reported by the comparison, not written astray)
+        const uint64_t nn_room = std::max(nn, np);
+        PAG_HIP_TRY(hipMalloc(&d_ncode, (nn_room + 1) * 4));
+        PAG_HIP_TRY(hipMalloc(&d_npos, (nn_room + 2) * 4));
+        PAG_HIP_TRY(hipMalloc(&d_nedge, (nn_room + 2) * 4));
+        PAG_HIP_TRY(hipMalloc(&d_vpos, (np + 4) * 8));
+        PAG_HIP_TRY(hipMalloc(&d_vcnt, (np + 1) * 2));
+        PAG_HIP_TRY(hipMalloc(&d_vnode, (np + 1) * 4));
+        PAG_HIP_TRY(hipMalloc(&d_eto, (ne + 4) * 4));
+        PAG_HIP_TRY(hipMalloc(&d_estep, (ne + 4) * 4));
+        PAG_HIP_TRY(hipMalloc(&d_bitmap, n_words * 8));
+        PAG_HIP_TRY(hipMalloc(&d_rank, n_words * 4));
+        PAG_HIP_TRY(hipMalloc(&d_tmp, tmp_bytes));
+        PAG_HIP_TRY(hipMemsetAsync(d_npos, 0, (nn + 2) * 4, s));
+        if (T) {
+            PAG_HIP_TRY(hipMemcpyAsync(d_tkey, tkey, T * 4, hipMemcpyHostToDevice, s));
+            PAG_HIP_TRY(hipMemcpyAsync(d_tval, tval, T * 8, hipMemcpyHostToDevice, s));
+            PAG_HIP_TRY(hipMemcpyAsync(d_tseg, tseg, T * 4, hipMemcpyHostToDevice, s));
+            PAG_HIP_TRY(hipMemcpyAsync(d_tcnt, tcnt, T * 2, hipMemcpyHostToDevice, s));
+        }
+        if (E) {
+            PAG_HIP_TRY(hipMemcpyAsync(d_ekey, ekey, E * 4, hipMemcpyHostToDevice, s));
+            PAG_HIP_TRY(hipMemcpyAsync(d_eval, eval, E * 8, hipMemcpyHostToDevice, s));
+            PAG_HIP_TRY(hipMemcpyAsync(d_eseg, eseg, E * 4, hipMemcpyHostToDevice, s));
+        }
+        TravView tv{};
+        if (region) {
+            uint32_t *d = (uint32_t *)d_iv;
+            if (n_civ) PAG_HIP_TRY(hipMemcpyAsync(d, region->ctg_iv, n_civ * 8, hipMemcpyHostToDevice, s));
+            if (n_riv) PAG_HIP_TRY(hipMemcpyAsync(d + 2 * n_civ, region->ref_iv, n_riv * 8, hipMemcpyHostToDevice, s));
+            tv.civ = d;
+            tv.n_civ = (uint32_t)n_civ;
+            tv.riv = d + 2 * n_civ;
+            tv.n_riv = (uint32_t)n_riv;
+        }
+        TravGraph G{};
+        G.n_nodes = nn;
+        G.n_pos = np;
+        G.n_edges = ne;
+        G.ncode = (uint32_t *)d_ncode;
+        G.npos_off = (uint32_t *)d_npos;
+        G.nedge_off = (uint32_t *)d_nedge;
+        G.vpos = (uint64_t *)d_vpos;
+        G.vcnt = (uint16_t *)d_vcnt;
+        G.vnode = (uint32_t *)d_vnode;
+        G.eto = (uint32_t *)d_eto;
+        G.estep = (uint32_t *)d_estep;
+        G.bitmap = (uint64_t *)d_bitmap;
+        G.rank = (uint32_t *)d_rank;
+        uint64_t c[3] = {nn, np, ne};
+        const int r = trav_compact((const uint32_t *)d_tkey, (const uint64_t *)d_tval, (const uint32_t *)d_tseg, (const uint16_t *)d_tcnt, T, (const uint32_t *)d_ekey,
+                                   (const uint64_t *)d_eval, (const uint32_t *)d_eseg, E, k, nn, np, ne, G, d_tmp, tmp_bytes, s, region ? &tv : nullptr, c);
+        if (r != PAG_OK) return r;
+        PAG_HIP_TRY(hipStreamSynchronize(s));
+        if (c[0] > nn || c[1] > np || c[2] > ne) {
+            set_error("pag_debug_trav_compact: the view holds more than the caller's counts");
+            return PAG_EFAULT;
+        }
+        if (c[1]) {
+            PAG_HIP_TRY(hipMemcpyAsync(vpos, d_vpos, c[1] * 8, hipMemcpyDeviceToHost, s));
+            PAG_HIP_TRY(hipMemcpyAsync(vcnt, d_vcnt, c[1] * 2, hipMemcpyDeviceToHost, s));
+            PAG_HIP_TRY(hipMemcpyAsync(vnode, d_vnode, c[1] * 4, hipMemcpyDeviceToHost, s));
+        }
+        if (c[0]) PAG_HIP_TRY(hipMemcpyAsync(ncode, d_ncode, c[0] * 4, hipMemcpyDeviceToHost, s));
+        PAG_HIP_TRY(hipMemcpyAsync(npos_off, d_npos, (c[0] + 1) * 4, hipMemcpyDeviceToHost, s));
+        PAG_HIP_TRY(hipMemcpyAsync(nedge_off, d_nedge, (c[0] + 1) * 4, hipMemcpyDeviceToHost, s));
+        if (c[2]) {
+            PAG_HIP_TRY(hipMemcpyAsync(eto, d_eto, c[2] * 4, hipMemcpyDeviceToHost, s));
+            PAG_HIP_TRY(hipMemcpyAsync(estep, d_estep, c[2] * 4, hipMemcpyDeviceToHost, s));
+        }
+        PAG_HIP_TRY(hipStreamSynchronize(s));
+        counts[0] = c[0];
+        counts[1] = c[1];
+        counts[2] = c[2];
+        return PAG_OK;
+    };
+    const int rc = run();
+    if (s) hipStreamSynchronize(s);
+    for (void *p : {d_tkey, d_tval, d_tseg, d_tcnt, d_ekey, d_eval, d_eseg, d_iv, d_vpos, d_vcnt, d_vnode, d_ncode, d_npos, d_nedge, d_eto, d_estep, d_bitmap, d_rank, d_tmp})
+        if (p) hipFree(p);
+    if (s) hipStreamDestroy(s);
+    hipSetDevice(before);
+    return rc;
+}

@@ -45,6 +45,26 @@ int pag_debug_owner_pick(const uint32_t *key, const uint64_t *val, uint64_t n, u
  * they build the same graph. */
 int pag_debug_shard_run_serial(pag_graph *g, const pag_build_input *in, const pag_region *regions, uint32_t n_ranks, uint32_t turn,
                                pag_build_stats *total, pag_serial_stats *st, int via_partition);
+/* The cut of the traversal graph, piece by piece (tests/test_gpu_view_cut.py against tests/view_rule.py).
+ * k_zone_bands (k5_view.hip) on HOST arrays: per zone z of zones[2 n_z] (sorted disjoint [lo, hi) pairs of contig coordinates) the
+ * lowest / highest reference coordinate among the slots of tval[T] whose contig coordinate lies in it; lo[z] all ones and hi[z] 0
+ * where there is none. */
+int pag_debug_zone_bands(const uint64_t *tval, uint64_t T, const uint32_t *zones, uint32_t n_z, uint32_t *lo, uint32_t *hi, int device);
+/* trav_compact (k5_view.hip) on HOST arrays in the layout of a slice (pag_shard_slice): the view's vertices and nodes out of the
+ * tuple slots, the edges of its nodes.  region: the interval tables of the view (its ref_open is not read), NULL: the whole graph.
+ * counts[3] goes in as (nodes, vertices, edges) of the graph — what pag_process counts: exact for region == NULL, upper bounds
+ * otherwise — and comes back as those of the view.  The outputs are sized by what went in: vpos / vcnt / vnode[vertices],
+ * ncode[nodes], npos_off / nedge_off[nodes + 1], eto / estep[edges]; the view's part of each is written.  Device buffers of its
+ * own, freed before it returns. */
+int pag_debug_trav_compact(uint32_t k, const uint32_t *tkey, const uint64_t *tval, const uint32_t *tseg, const uint16_t *tcnt, uint64_t T,
+                           const uint32_t *ekey, const uint64_t *eval, const uint32_t *eseg, uint64_t E, const pag_region *region,
+                           uint64_t *vpos, uint16_t *vcnt, uint32_t *vnode, uint32_t *ncode, uint32_t *npos_off, uint32_t *nedge_off,
+                           uint32_t *eto, uint32_t *estep, uint64_t *counts, int device);
+/* trav_view_region (trav_prepare_host.hpp) for the handle's current graph under the current PAG_VIEW_HALO / PAG_VIEW_MARGIN: what
+ * pag_travel_prepare_for(orient) would cut the view to.  sizes[2] = pairs in civ / riv; civ[2 cap], riv[2 cap], ropen[2 cap] are
+ * filled when both fit `cap` pairs (PAG_ERANGE otherwise, sizes set). */
+int pag_debug_view_region(pag_graph *g, const uint32_t *ctg_len, uint64_t n_ctgs, const int32_t *orient, const uint32_t *ref_len,
+                          uint64_t n_refs, double start_split, uint32_t *civ, uint32_t *riv, uint8_t *ropen, uint64_t *sizes, uint64_t cap);
 
 /* ---- libpagraph_host.so ---- */
 /* one record's column classes / one sequence packed, by the production path or by the scalar loop alone */
