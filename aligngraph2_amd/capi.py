@@ -41,7 +41,12 @@ DTYPES = {
                              ("n_radv", "<u4"), ("forward", "<u4")]),
     "pag_path_node": np.dtype([("code", "<u4"), ("ctg", "<u4"), ("ref", "<u4"), ("cnt", "<u2"), ("reserved", "<u2"),
                                ("step", "<i4"), ("vid", "<u4")]),
+    # include/pagraph_debug.h: a TravContig as the hooks on constructed graphs take it
+    "pag_debug_trav_contig": np.dtype([("nodes_off", "<u8"), ("gbits_off", "<u8"), ("gset_off", "<u8"), ("n_kmers", "<u4"),
+                                       ("ctg_left", "<u4"), ("ctg_right", "<u4"), ("in_lo", "<u4"), ("in_hi", "<u4"), ("g_lo", "<u4"),
+                                       ("g_hi", "<u4"), ("gmask", "<u4")]),
 }
+PAG_DEBUG_NULL = 0xFFFFFFFFFFFFFFFF  # (pagraph_debug.h; as a C long long it is -1, so it is not among CONSTANTS)
 
 # ---- struct mirrors -----------------------------------------------------------------------------------------------------------
 _u32, _i32, _u64, _f64, _vp = C.c_uint32, C.c_int32, C.c_uint64, C.c_double, C.c_void_p
@@ -156,10 +161,17 @@ class TraverseStats(C.Structure):
                 ("walk_classifications", _u64)]
 
 
-STRUCTS = {s._c_name_: s for s in (PagSeqs, PagAlnDb, PagBuildInput, PagRawDb, PagRawInput, BuildStats, Csr, ShardSlice, Region,
-                                   SerialStats, TravelParams, TravelStats, PagSucc, CnsAln, CnsPart, KmerCountResult, TraverseStats)}
+class DebugTravGraph(C.Structure):
+    _c_name_ = "pag_debug_trav_graph"
+    _fields_ = [("n_nodes", _u64), ("n_pos", _u64), ("k", _u32), ("reserved", _u32), ("ncode", _vp), ("npos_off", _vp), ("vpos", _vp),
+                ("vcnt", _vp), ("vnode", _vp), ("uold", _vp), ("newid", _vp), ("upos", _vp), ("ucnt", _vp), ("bitmap", _vp), ("rank", _vp)]
 
-# structs of the two headers that are deliberately mirrored neither in STRUCTS nor in DTYPES: C name -> why.  (The opaque
+
+STRUCTS = {s._c_name_: s for s in (PagSeqs, PagAlnDb, PagBuildInput, PagRawDb, PagRawInput, BuildStats, Csr, ShardSlice, Region,
+                                   SerialStats, TravelParams, TravelStats, PagSucc, CnsAln, CnsPart, KmerCountResult, TraverseStats,
+                                   DebugTravGraph)}
+
+# structs of the headers that are deliberately mirrored neither in STRUCTS nor in DTYPES: C name -> why.  (The opaque
 # handles pag_graph and pag_comm have no body to mirror.)
 NOT_MIRRORED = {}
 
@@ -259,6 +271,14 @@ SIGNATURES = {
     "pag_debug_trav_compact": (_int, [_u32, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _region, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                       _vp, _int]),
     "pag_debug_view_region": (_int, [_vp, _vp, _u64, _vp, _vp, _u64, _f64, _vp, _vp, _vp, _vp, _u64]),
+    "pag_debug_trav_bounds": (_int, [_vp, _vp, _u32, _vp, _vp, _u32, _int]),
+    "pag_debug_ctg_nodes": (_int, [_vp, _vp, _u64, _vp, _u32, _u32, _vp, _u64, _int]),
+    "pag_debug_trav_seeds": (_int, [_vp, _int, _vp, _u32, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _u32, _u64, _vp, _u64, _u32, _int]),
+    "pag_debug_pack_paths": (_int, [_vp, _vp, _vp, _vp, _u64, _vp, _u32, _u64, _vp, _u64, _int]),
+    "pag_debug_commit": (_int, [_vp, _u64, _u32, _u32, _vp, _u64, _u64, _vp, _u32, _int]),
+    "pag_debug_clear_ranges": (_int, [_vp, _u64, _vp, _u64, _int]),
+    "pag_debug_concat_parts": (_int, [_vp, _vp, _u64, _vp, _u32, _vp, _vp, _u64, _u32, _int]),
+    "pag_debug_gathers": (_int, [_vp, _int, _vp, _vp, _u64, _u32, _vp, _int]),
     "pagh_debug_classify_columns": (None, [_cs, _u64, _cs, _u64, _vp, _vp, _vp, _int]),
     "pagh_debug_pack_bases": (None, [_cs, _u64, _vp, _int]),
 }

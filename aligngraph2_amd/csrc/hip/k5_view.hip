@@ -13,6 +13,7 @@
 #include "pag_travel.hpp"
 #include "pagraph_debug.h"
 #include "trav_device.hpp"
+#include "trav_hook.hpp"
 
 namespace pagdev {
 
@@ -772,4 +773,37 @@ extern "C" int pag_debug_trav_compact(uint32_t k, const uint32_t *tkey, const ui
     if (s) hipStreamDestroy(s);
     hipSetDevice(before);
     return rc;
+}
+
+// k_ctg_nodes on caller-given HOST arrays (trav_hook.hpp).  The device copy of `packed` is as long as setup_contigs makes it:
+// packed_bytes + 64, the 64 zeroed.  The kernel's read of words[w + 1] — the word behind the one a k-mer starts in, read
+// whether the k-mer reaches into it or not — stays inside the caller's packed_bytes as long as pag_seqs' own padding (16
+// readable bytes behind the last strand) is there: it ends at most 8 bytes behind the strand's last byte.  That is what is
+// checked here per job, so the 64 bytes are never what makes a launch safe.
+extern "C" int pag_debug_ctg_nodes(const pag_debug_trav_graph *g, const uint8_t *packed, uint64_t packed_bytes, const uint64_t *jobs, uint32_t n_jobs,
+                                   uint32_t max_len, uint32_t *out, uint64_t n_out, int device) {
+    if (!g || !g->bitmap || !g->rank || (packed_bytes && !packed) || (n_jobs && !jobs) || (n_out && !out)) return PAG_EINVAL;
+    const uint32_t k = g->k;
+    std::vector<TravCtgNodesJob> cj(n_jobs);
+    for (uint32_t j = 0; j < n_jobs; ++j) {
+        const uint64_t byte_off = jobs[4 * j], out_off = jobs[4 * j + 1], len = jobs[4 * j + 2];
+        if (len > max_len || (byte_off & 3u)) return PAG_EINVAL;
+        const uint64_t n_kmers = len >= k ? len - k + 1 : 0;
+        if (out_off > n_out || n_kmers > n_out - out_off) return PAG_EINVAL;
+        if (n_kmers && (byte_off > packed_bytes || 4 * (((len - k) >> 4) + 2) > packed_bytes - byte_off)) return PAG_EINVAL;
+        cj[j] = TravCtgNodesJob{byte_off, out_off, (uint32_t)len, jobs[4 * j + 3] ? 1 : 0};
+    }
+    HookDev D;
+    TravGraph G;
+    int rc;
+    if ((rc = D.open(device)) || (rc = hook_upload_graph(D, g, &G))) return rc;
+    uint8_t *d_packed = nullptr;
+    uint32_t *d_out = nullptr;
+    TravCtgNodesJob *d_jobs = nullptr;
+    if ((rc = D.up(packed, packed_bytes, &d_packed, 64)) || (rc = D.up((const uint32_t *)out, n_out, &d_out)) ||
+        (rc = D.up((const TravCtgNodesJob *)cj.data(), (uint64_t)n_jobs, &d_jobs)))
+        return rc;
+    trav_launch_ctg_nodes(d_packed, d_jobs, n_jobs, max_len, k, G, d_out, D.s);
+    if ((rc = D.down(out, d_out, n_out))) return rc;
+    return D.finish();
 }

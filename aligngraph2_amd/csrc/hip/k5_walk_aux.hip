@@ -11,6 +11,7 @@
 #include "pag_device.hpp"
 #include "pag_travel.hpp"
 #include "trav_device.hpp"
+#include "trav_hook.hpp"
 
 namespace pagdev {
 
@@ -175,6 +176,9 @@ __global__ __launch_bounds__(64) void k_seed_window(TravGraph G, const TravConti
 // visited set.  Ties: the lowest offset, then position order.  One wave per request; out = (old vertex id, contig
 // coordinate, abundance) or (PAG_NONE, 0, 0).  Which vertex is picked has no influence on the results of the
 // traversal, only on how soon the walk that arrives from behind meets the piece started here.
+// The visited test reads the bitmap alone: a vertex on the strand has its new id in [g_lo, g_hi) as k_ranges leaves them, so the
+// hash set holds none of the candidates.  The tie-breaks are 20-bit fields: they wrap for a window of more than 2^20 offsets or a
+// k-mer with more than 2^20 positions, and the pick among equal abundances is then another one (still a valid checkpoint).
 __global__ __launch_bounds__(64) void k_checkpoints(TravGraph G, const TravContig *__restrict__ ctgs, const TravSeedReq *__restrict__ reqs,
                                                     uint32_t n_req, uint64_t dev, uint32_t *__restrict__ out) {
     const uint32_t r = blockIdx.x;
@@ -363,7 +367,9 @@ void trav_launch_ranges(TravGraph G, TravContig *ctgs, uint32_t n, hipStream_t s
     if (n) k_ranges<<<dim3((n + 63) / 64), dim3(64), 0, s>>>(G, ctgs, n);
 }
 
-// blockIdx.y = range; 16 bytes per lane and turn where the range allows (the job buffers are 256-byte aligned), bytes at its edges
+// blockIdx.y = range; 16 bytes per lane and turn where the range allows (the job buffers are 256-byte aligned), bytes at its edges.
+// The byte at address a becomes byte (a & 3) of `word`, at the edges as in the body: a range on a 4-byte boundary is filled with
+// whole copies of `word` whatever its bytes are, wherever its first 16-byte line begins.
 __global__ void k_clear_ranges(const TravClear *__restrict__ ranges) {
     const TravClear c = ranges[blockIdx.y];
     uint8_t *p = as_global((uint8_t *)c.p);  // (device memory: global stores, not flat ones)
@@ -373,8 +379,9 @@ __global__ void k_clear_ranges(const TravClear *__restrict__ ranges) {
     const uint4 w = make_uint4(c.word, c.word, c.word, c.word);
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (uint64_t)gridDim.x * blockDim.x) q[i] = w;
     if (blockIdx.x == 0) {
-        if (threadIdx.x < h) p[threadIdx.x] = (uint8_t)c.word;
-        if (threadIdx.x < tail) p[h + (n16 << 4) + threadIdx.x] = (uint8_t)c.word;
+        auto byte_at = [&](const uint8_t *a) { return (uint8_t)(c.word >> (8u * (uint32_t)((uintptr_t)a & 3u))); };
+        if (threadIdx.x < h) p[threadIdx.x] = byte_at(p + threadIdx.x);
+        if (threadIdx.x < tail) p[h + (n16 << 4) + threadIdx.x] = byte_at(p + h + (n16 << 4) + threadIdx.x);
     }
 }
 int trav_clear_ranges(const TravClear *ranges_dev, size_t n, hipStream_t s) {
@@ -411,3 +418,247 @@ void trav_launch_gather_vertices(TravGraph G, const uint32_t *vids, uint32_t n, 
 }
 
 }  // namespace pagdev
+
+using namespace pagdev;
+
+// test hooks (include/pagraph_debug.h): the kernels above through their production launchers, on caller-given HOST arrays with
+// device buffers of their own (trav_hook.hpp).  Each refuses what would let a kernel leave those buffers or never end.
+namespace {
+// TravContig records out of their mirrors: nodes / gbits / gset patched in from the uploaded arrays
+int hook_contigs(const pag_debug_trav_contig *ctgs, uint32_t n_ctgs, uint64_t n_graph_nodes, const uint32_t *nodes, uint64_t n_node_words,
+                 uint64_t n_gbits, const uint32_t *gset, uint64_t n_gset, const uint32_t *d_nodes, uint32_t *d_gbits, uint32_t *d_gset,
+                 std::vector<TravContig> &tc) {
+    if (n_ctgs && !ctgs) return PAG_EINVAL;
+    for (uint64_t i = 0; i < n_node_words; ++i)
+        if (nodes[i] != PAG_NONE && nodes[i] >= n_graph_nodes) return PAG_EINVAL;
+    tc.assign(n_ctgs, TravContig{});
+    for (uint32_t i = 0; i < n_ctgs; ++i) {
+        const pag_debug_trav_contig &m = ctgs[i];
+        TravContig &t = tc[i];
+        if (m.n_kmers && (m.nodes_off > n_node_words || m.n_kmers > n_node_words - m.nodes_off)) return PAG_EINVAL;
+        if (m.g_hi < m.g_lo || m.in_hi < m.in_lo) return PAG_EINVAL;
+        t.nodes = d_nodes + m.nodes_off;
+        t.n_kmers = m.n_kmers;
+        t.ctg_left = m.ctg_left;
+        t.ctg_right = m.ctg_right;
+        t.in_lo = m.in_lo;
+        t.in_hi = m.in_hi;
+        t.g_lo = m.g_lo;
+        t.g_hi = m.g_hi;
+        t.gmask = m.gmask;
+        if (m.gbits_off != PAG_DEBUG_NULL) {
+            const uint64_t words = ((uint64_t)(m.g_hi - m.g_lo) + 31) / 32;
+            if (m.gbits_off > n_gbits || words > n_gbits - m.gbits_off) return PAG_EINVAL;
+            t.gbits = d_gbits + m.gbits_off;
+        }
+        if (m.gset_off != PAG_DEBUG_NULL) {
+            const uint64_t cap = (uint64_t)m.gmask + 1;
+            if ((cap & (cap - 1)) || m.gset_off > n_gset || cap > n_gset - m.gset_off) return PAG_EINVAL;
+            bool free_slot = false;  // (a lookup ends at a key or at an empty slot)
+            for (uint64_t x = 0; x < cap && !free_slot; ++x) free_slot = gset[m.gset_off + x] == HS_EMPTY;
+            if (!free_slot) return PAG_EINVAL;
+            t.gset = d_gset + m.gset_off;
+        }
+    }
+    return PAG_OK;
+}
+}  // namespace
+
+extern "C" int pag_debug_trav_bounds(const pag_debug_trav_graph *g, const uint32_t *coords, uint32_t n, uint32_t *out, pag_debug_trav_contig *ctgs,
+                                     uint32_t n_ctgs, int device) {
+    if (!g || (g->n_pos && !g->upos) || (n && (!coords || !out)) || (n_ctgs && !ctgs)) return PAG_EINVAL;
+    HookDev D;
+    TravGraph G;
+    int rc;
+    if ((rc = D.open(device)) || (rc = hook_upload_graph(D, g, &G))) return rc;
+    uint32_t *d_coords = nullptr, *d_out = nullptr;
+    TravContig *d_tc = nullptr;
+    std::vector<TravContig> tc(n_ctgs, TravContig{});
+    for (uint32_t i = 0; i < n_ctgs; ++i) {
+        tc[i].ctg_left = ctgs[i].ctg_left;
+        tc[i].ctg_right = ctgs[i].ctg_right;
+        tc[i].in_lo = ctgs[i].in_lo;
+        tc[i].in_hi = ctgs[i].in_hi;
+        tc[i].g_lo = ctgs[i].g_lo;
+        tc[i].g_hi = ctgs[i].g_hi;
+    }
+    if ((rc = D.up(coords, n, &d_coords)) || (rc = D.up((const uint32_t *)out, n, &d_out)) || (rc = D.up((const TravContig *)tc.data(), n_ctgs, &d_tc))) return rc;
+    trav_launch_id_bounds(G, d_coords, n, d_out, D.s);
+    trav_launch_ranges(G, d_tc, n_ctgs, D.s);
+    if ((rc = D.down(out, d_out, n)) || (rc = D.down(tc.data(), d_tc, n_ctgs)) || (rc = D.finish())) return rc;
+    for (uint32_t i = 0; i < n_ctgs; ++i) {
+        ctgs[i].in_lo = tc[i].in_lo;
+        ctgs[i].in_hi = tc[i].in_hi;
+        ctgs[i].g_lo = tc[i].g_lo;
+        ctgs[i].g_hi = tc[i].g_hi;
+    }
+    return PAG_OK;
+}
+
+extern "C" int pag_debug_trav_seeds(const pag_debug_trav_graph *g, int which, const pag_debug_trav_contig *ctgs, uint32_t n_ctgs, const uint32_t *nodes,
+                                    uint64_t n_node_words, const uint32_t *gbits, uint64_t n_gbits, const uint32_t *gset, uint64_t n_gset,
+                                    const uint64_t *reqs, uint32_t n_req, uint64_t dev, uint32_t *out, uint64_t out_words, uint32_t stride, int device) {
+    if (!g || which < 0 || which > 2 || !g->npos_off || (g->n_pos && (!g->vpos || !g->newid || !g->vcnt)) || (n_node_words && !nodes) ||
+        (n_gbits && !gbits) || (n_gset && !gset) || !out)
+        return PAG_EINVAL;
+    const uint64_t need = which == 0 ? (uint64_t)n_ctgs * stride : which == 1 ? (uint64_t)n_req * TRAV_SEED_PARTS * stride : 3ull * n_req;
+    if ((which != 2 && stride < 2) || out_words < need || (which != 0 && n_req && !reqs)) return PAG_EINVAL;
+    std::vector<TravSeedReq> rq(which == 0 ? 0 : n_req);
+    for (size_t r = 0; r < rq.size(); ++r) {
+        if (reqs[4 * r] >= n_ctgs) return PAG_EINVAL;
+        rq[r].ctg = (uint32_t)reqs[4 * r];
+        rq[r].pad = 0;
+        rq[r].left = reqs[4 * r + 1];
+        rq[r].right = reqs[4 * r + 2];
+        rq[r].pos = reqs[4 * r + 3];
+    }
+    HookDev D;
+    TravGraph G;
+    int rc;
+    if ((rc = D.open(device)) || (rc = hook_upload_graph(D, g, &G))) return rc;
+    uint32_t *d_nodes = nullptr, *d_gbits = nullptr, *d_gset = nullptr, *d_out = nullptr;
+    TravContig *d_tc = nullptr;
+    TravSeedReq *d_rq = nullptr;
+    if ((rc = D.up(nodes, n_node_words, &d_nodes)) || (rc = D.up(gbits, n_gbits, &d_gbits)) || (rc = D.up(gset, n_gset, &d_gset)) ||
+        (rc = D.up((const uint32_t *)out, out_words, &d_out)))
+        return rc;
+    std::vector<TravContig> tc;
+    if ((rc = hook_contigs(ctgs, n_ctgs, g->n_nodes, nodes, n_node_words, n_gbits, gset, n_gset, d_nodes, d_gbits, d_gset, tc))) return rc;
+    if ((rc = D.up((const TravContig *)tc.data(), n_ctgs, &d_tc)) || (rc = D.up((const TravSeedReq *)rq.data(), rq.size(), &d_rq))) return rc;
+    if (which == 0) trav_launch_seed_first(G, d_tc, n_ctgs, dev, d_out, stride, D.s);
+    else if (which == 1) trav_launch_seed_window(G, d_tc, d_rq, n_req, dev, d_out, stride, D.s);
+    else trav_launch_checkpoints(G, d_tc, d_rq, n_req, dev, d_out, D.s);
+    if ((rc = D.down(out, d_out, out_words))) return rc;
+    return D.finish();
+}
+
+extern "C" int pag_debug_pack_paths(const pag_debug_trav_graph *g, const uint32_t *seq_v, const uint32_t *seq_s, const uint64_t *seq_x, uint64_t n_seq,
+                                    const uint64_t *descs, uint32_t n, uint64_t max_len, uint32_t *out, uint64_t out_words, int device) {
+    if (!g || !g->upos || (n_seq && (!seq_v || !seq_s)) || (n && !descs) || !out || n > 65535u) return PAG_EINVAL;
+    for (uint64_t i = 0; i < n_seq; ++i)
+        if (seq_v[i] >= g->n_pos) return PAG_EINVAL;
+    for (uint32_t j = 0; j < n; ++j) {
+        const uint64_t from = descs[4 * j], len = descs[4 * j + 1], off = descs[4 * j + 2];
+        const bool leap = descs[4 * j + 3] != 0;
+        if (from > n_seq || len > n_seq - from || len > max_len || (leap && !seq_x)) return PAG_EINVAL;
+        if (off > out_words || trav_pack_words(len, leap) > out_words - off) return PAG_EINVAL;
+    }
+    HookDev D;
+    TravGraph G;
+    int rc;
+    if ((rc = D.open(device)) || (rc = hook_upload_graph(D, g, &G))) return rc;
+    uint32_t *d_v = nullptr, *d_s = nullptr, *d_out = nullptr;
+    uint64_t *d_x = nullptr;
+    TravPackDesc *d_desc = nullptr;
+    if ((rc = D.up(seq_v, n_seq, &d_v)) || (rc = D.up(seq_s, n_seq, &d_s)) || (rc = D.up(seq_x, seq_x ? n_seq : 0, &d_x)) ||
+        (rc = D.up((const uint32_t *)out, out_words, &d_out)))
+        return rc;
+    std::vector<TravPackDesc> pd(n);
+    for (uint32_t j = 0; j < n; ++j) {
+        pd[j].seq_v = d_v + descs[4 * j];
+        pd[j].seq_s = d_s + descs[4 * j];
+        pd[j].len = descs[4 * j + 1];
+        pd[j].off = descs[4 * j + 2];
+        pd[j].seq_x = descs[4 * j + 3] ? d_x + descs[4 * j] : nullptr;
+    }
+    if ((rc = D.up((const TravPackDesc *)pd.data(), n, &d_desc))) return rc;
+    trav_launch_pack_paths(G, d_desc, n, max_len, d_out, D.s);
+    if ((rc = D.down(out, d_out, out_words))) return rc;
+    return D.finish();
+}
+
+extern "C" int pag_debug_commit(const uint32_t *seq_v, uint64_t len, uint32_t in_lo, uint32_t in_hi, uint32_t *gbits, uint64_t n_gbits, uint64_t gbits_off,
+                                uint32_t *gset, uint32_t ncap, int device) {
+    if ((len && !seq_v) || in_hi < in_lo || !gset || !ncap || (ncap & (ncap - 1)) || (n_gbits && !gbits)) return PAG_EINVAL;
+    if (gbits_off > n_gbits || ((uint64_t)(in_hi - in_lo) + 31) / 32 > n_gbits - gbits_off) return PAG_EINVAL;
+    {   // an insert ends at its key or at an empty slot: more empty slots than distinct keys to come
+        std::vector<uint32_t> outside;
+        for (uint64_t i = 0; i < len; ++i)
+            if (seq_v[i] < in_lo || seq_v[i] >= in_hi) outside.push_back(seq_v[i]);
+        std::sort(outside.begin(), outside.end());
+        const uint64_t distinct = (uint64_t)(std::unique(outside.begin(), outside.end()) - outside.begin());
+        uint64_t empty = 0;
+        for (uint32_t x = 0; x < ncap; ++x) empty += gset[x] == HS_EMPTY;
+        if (empty <= distinct) return PAG_EINVAL;
+    }
+    HookDev D;
+    int rc;
+    if ((rc = D.open(device))) return rc;
+    uint32_t *d_v = nullptr, *d_bits = nullptr, *d_set = nullptr;
+    if ((rc = D.up(seq_v, len, &d_v)) || (rc = D.up((const uint32_t *)gbits, n_gbits, &d_bits)) || (rc = D.up((const uint32_t *)gset, (uint64_t)ncap, &d_set))) return rc;
+    trav_launch_commit(d_v, len, in_lo, in_hi, d_bits + gbits_off, d_set, ncap - 1, D.s);
+    if ((rc = D.down(gbits, d_bits, n_gbits)) || (rc = D.down(gset, d_set, (uint64_t)ncap))) return rc;
+    return D.finish();
+}
+
+extern "C" int pag_debug_clear_ranges(uint8_t *buf, uint64_t bytes, const uint64_t *ranges, uint64_t n, int device) {
+    if ((bytes && !buf) || (n && !ranges)) return PAG_EINVAL;
+    for (uint64_t i = 0; i < n; ++i)
+        if (ranges[3 * i] > bytes || ranges[3 * i + 1] > bytes - ranges[3 * i] || ranges[3 * i + 2] > 0xFFFFFFFFull) return PAG_EINVAL;
+    HookDev D;
+    int rc;
+    if ((rc = D.open(device))) return rc;
+    uint8_t *d_buf = nullptr;
+    TravClear *d_r = nullptr;
+    if ((rc = D.up((const uint8_t *)buf, bytes, &d_buf, 256))) return rc;
+    if (((uintptr_t)d_buf & 255u) != 0) {
+        set_error("pag_debug_clear_ranges: the device buffer does not start on a 256-byte boundary");
+        return PAG_EFAULT;
+    }
+    std::vector<TravClear> rs(n);
+    for (uint64_t i = 0; i < n; ++i) rs[i] = TravClear{d_buf + ranges[3 * i], ranges[3 * i + 1], (uint32_t)ranges[3 * i + 2], 0u};
+    if ((rc = D.up((const TravClear *)rs.data(), n, &d_r))) return rc;
+    if (n && (rc = trav_clear_ranges(d_r, n, D.s))) return rc;
+    if ((rc = D.down(buf, d_buf, bytes))) return rc;
+    return D.finish();
+}
+
+extern "C" int pag_debug_concat_parts(const uint32_t *src_v, const uint32_t *src_s, uint64_t n_src, const uint64_t *parts, uint32_t n_parts, uint32_t *out_v,
+                                      uint32_t *out_s, uint64_t n_out, uint32_t first_step, int device) {
+    if ((n_src && (!src_v || !src_s)) || (n_parts && !parts) || (n_out && (!out_v || !out_s))) return PAG_EINVAL;
+    for (uint32_t i = 0; i < n_parts; ++i) {
+        const uint64_t from = parts[3 * i], start = parts[3 * i + 1], m = parts[3 * i + 2];
+        if (from > n_src || m > n_src - from || start > n_out || m > n_out - start) return PAG_EINVAL;
+    }
+    HookDev D;
+    int rc;
+    if ((rc = D.open(device))) return rc;
+    uint32_t *d_sv = nullptr, *d_ss = nullptr, *d_ov = nullptr, *d_os = nullptr;
+    TravConcatPart *d_p = nullptr;
+    if ((rc = D.up(src_v, n_src, &d_sv)) || (rc = D.up(src_s, n_src, &d_ss)) || (rc = D.up((const uint32_t *)out_v, n_out, &d_ov)) ||
+        (rc = D.up((const uint32_t *)out_s, n_out, &d_os)))
+        return rc;
+    std::vector<TravConcatPart> ps(n_parts);
+    for (uint32_t i = 0; i < n_parts; ++i) ps[i] = TravConcatPart{d_sv + parts[3 * i], d_ss + parts[3 * i], parts[3 * i + 1], parts[3 * i + 2]};
+    if ((rc = D.up((const TravConcatPart *)ps.data(), (uint64_t)n_parts, &d_p))) return rc;
+    trav_launch_concat_parts(d_p, n_parts, d_ov, d_os, first_step, D.s);
+    if ((rc = D.down(out_v, d_ov, n_out)) || (rc = D.down(out_s, d_os, n_out))) return rc;
+    return D.finish();
+}
+
+extern "C" int pag_debug_gathers(const pag_debug_trav_graph *g, int which, const uint32_t *seq_v, const uint32_t *seq_s, uint64_t len, uint32_t max_blocks,
+                                 void *out, int device) {
+    if (!g || which < 0 || which > 2 || (len && (!seq_v || !out)) || (which == 1 && len && !seq_s) || (which == 2 && len > 0xFFFFFFF0ull)) return PAG_EINVAL;
+    if (which == 0 ? !g->upos : (!g->vpos || !g->vcnt || !g->vnode || !g->ncode || (which == 1 && !g->uold))) return PAG_EINVAL;
+    for (uint64_t i = 0; i < len; ++i)
+        if (seq_v[i] >= g->n_pos) return PAG_EINVAL;
+    HookDev D;
+    TravGraph G;
+    int rc;
+    if ((rc = D.open(device)) || (rc = hook_upload_graph(D, g, &G))) return rc;
+    uint32_t *d_v = nullptr, *d_s = nullptr;
+    if ((rc = D.up(seq_v, len, &d_v)) || (rc = D.up(seq_s, seq_s ? len : 0, &d_s))) return rc;
+    if (which == 0) {
+        uint32_t *d_out = nullptr;
+        if ((rc = D.up((const uint32_t *)out, len, &d_out))) return rc;
+        trav_launch_gather_pc(G, d_v, len, d_out, D.s);
+        if ((rc = D.down((uint32_t *)out, d_out, len))) return rc;
+    } else {
+        pag_path_node *d_out = nullptr;
+        if ((rc = D.up((const pag_path_node *)out, len, &d_out))) return rc;
+        if (which == 1) trav_launch_gather_path(G, d_v, d_s, len, d_out, D.s, max_blocks);
+        else trav_launch_gather_vertices(G, d_v, (uint32_t)len, d_out, D.s);
+        if ((rc = D.down((pag_path_node *)out, d_out, len))) return rc;
+    }
+    return D.finish();
+}

@@ -217,7 +217,8 @@ size_t trav_mark_incomplete_tmp_bytes(uint32_t n_iv);
 
 int trav_order(TravGraph G, uint32_t *key, uint64_t *val, uint32_t *key2, uint64_t *val2, void *sort_tmp, uint64_t *n_zero, int ctg_bits,
                int ref_bits, hipStream_t s);
-// device ranges cleared by one launch (the buffers of the walk jobs of a batch): `bytes` bytes at p set to the bytes of `word`
+// device ranges cleared by one launch (the buffers of the walk jobs of a batch): `bytes` bytes at p set to the bytes of `word`, the
+// byte at address a to byte (a & 3) of it — whole copies of `word` from any p on a 4-byte boundary (k_clear_ranges)
 struct TravClear {
     void *p;
     uint64_t bytes;

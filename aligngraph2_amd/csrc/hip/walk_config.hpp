@@ -28,6 +28,7 @@ struct WalkConfig {
     bool check_aggs = false;          // PAG_DEBUG_CHECK_AGGS
     int debug_seqcap = 0;             // PAG_DEBUG_SEQCAP (> 0: tiny initial walk buffers)
     int debug_ring = 0;               // PAG_DEBUG_RING (> 0: job rings of that many entries)
+    uint32_t debug_seed_stride = 0;   // PAG_DEBUG_SEED_STRIDE (> 0: the first stride of the re-seed windows, a power of two >= 4: the search-again path of reseed())
     bool debug_deliver_late = false;  // PAG_DEBUG_DELIVER_LATE: no contig is delivered (or put together on the device) while the walks run: all of them are left to the epilogue
     uint64_t debug_emit_cap = 0;      // PAG_DEBUG_EMIT_CAP (> 0: the first emission stream of the successor records has that many slots: the grow-and-repeat path)
     // ---- pieces
@@ -66,6 +67,10 @@ struct WalkConfig {
         c.check_aggs = given("PAG_DEBUG_CHECK_AGGS");
         if (u64("PAG_DEBUG_SEQCAP", &x)) c.debug_seqcap = (int)std::max<uint64_t>(16, std::min<uint64_t>(x, 1u << 30));
         if (u64("PAG_DEBUG_RING", &x)) c.debug_ring = (int)std::max<uint64_t>(4, std::min<uint64_t>(x, 1u << 30));
+        if (u64("PAG_DEBUG_SEED_STRIDE", &x) && x) {
+            c.debug_seed_stride = 4;
+            while (c.debug_seed_stride < std::min<uint64_t>(x, 1u << 28)) c.debug_seed_stride *= 2;
+        }
         u64("PAG_DEBUG_EMIT_CAP", &c.debug_emit_cap);
         c.debug_deliver_late = given("PAG_DEBUG_DELIVER_LATE");
         c.pieces = !off("PAG_WALK_PIECES");

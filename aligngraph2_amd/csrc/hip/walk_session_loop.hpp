@@ -563,7 +563,7 @@ struct WalkSession : WalkRounds {
         int rc;
         if (!reqs.empty()) {
             const uint32_t PARTS = TRAV_SEED_PARTS;
-            uint32_t WSTRIDE = 2048;  // words per part of a request
+            uint32_t WSTRIDE = cfg.debug_seed_stride ? cfg.debug_seed_stride : 2048;  // words per part of a request (tests: PAG_DEBUG_SEED_STRIDE)
             std::vector<uint32_t> wb;
             for (;;) {  // (a part with more candidates than the stride is searched again with a larger one)
                 const size_t words = (size_t)reqs.size() * PARTS * WSTRIDE;
@@ -590,7 +590,9 @@ struct WalkSession : WalkRounds {
                     set_error("pag_travel: seed window with %u candidates", most);
                     return fail(PAG_ENOMEM);
                 }
-                WSTRIDE = (uint32_t)pow2_at_least((uint64_t)most + 2);
+                const uint32_t again = (uint32_t)pow2_at_least((uint64_t)most + 2);
+                if (timing) std::fprintf(stderr, "[timing] seed windows: a part of %zu requests has %u candidates, searched again with stride %u -> %u\n", reqs.size(), most, WSTRIDE, again);
+                WSTRIDE = again;
             }
             std::vector<uint32_t> vids;
             std::vector<size_t> cnt(reqs.size());

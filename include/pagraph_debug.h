@@ -66,6 +66,66 @@ int pag_debug_trav_compact(uint32_t k, const uint32_t *tkey, const uint64_t *tva
 int pag_debug_view_region(pag_graph *g, const uint32_t *ctg_len, uint64_t n_ctgs, const int32_t *orient, const uint32_t *ref_len,
                           uint64_t n_refs, double start_split, uint32_t *civ, uint32_t *riv, uint8_t *ropen, uint64_t *sizes, uint64_t cap);
 
+/* The kernels around the walker waves (k5_walk_aux.hip, and k_ctg_nodes of k5_view.hip), one by one, on CONSTRUCTED graphs
+ * (tests/test_gpu_walk_aux.py against tests/walk_aux_rule.py).  No handle: a traversal graph is described by host arrays, as the
+ * kernels read it; an array a kernel does not read may be NULL.  Every hook uploads into device buffers of its own, calls the
+ * PRODUCTION launcher (trav_launch_*, trav_clear_ranges) and frees the buffers before it returns.  Output arrays are uploaded as
+ * the caller filled them and copied back whole: what a kernel did not write is what the caller put there.  The hooks refuse
+ * (PAG_EINVAL) what would make a kernel read or write outside these buffers or never end. */
+typedef struct pag_debug_trav_graph {
+    uint64_t n_nodes, n_pos;
+    uint32_t k, reserved;
+    const uint32_t *ncode;    /* [n_nodes] */
+    const uint32_t *npos_off; /* [n_nodes + 1] */
+    const uint64_t *vpos;     /* [n_pos] ctg << 32 | ref, k-mer-major */
+    const uint16_t *vcnt;     /* [n_pos] */
+    const uint32_t *vnode;    /* [n_pos] */
+    const uint32_t *uold;     /* [n_pos] new id -> vertex */
+    const uint32_t *newid;    /* [n_pos] vertex -> new id */
+    const uint64_t *upos;     /* [n_pos] positions by new id */
+    const uint32_t *ucnt;     /* [n_pos] abundances by new id */
+    const uint64_t *bitmap;   /* [(4^k + 63) / 64] */
+    const uint32_t *rank;     /* [(4^k + 63) / 64] */
+} pag_debug_trav_graph;
+/* the fields of a TravContig (pag_travel.hpp) these kernels read, by value; its three pointers as word offsets into the arrays
+ * `nodes`, `gbits`, `gset` given beside the records (PAG_DEBUG_NULL: a null pointer) */
+#define PAG_DEBUG_NULL 0xFFFFFFFFFFFFFFFFull
+typedef struct pag_debug_trav_contig {
+    uint64_t nodes_off, gbits_off, gset_off;
+    uint32_t n_kmers, ctg_left, ctg_right, in_lo, in_hi, g_lo, g_hi, gmask;
+} pag_debug_trav_contig;
+/* k_id_bounds over coords[n] -> out[n], then k_ranges over ctgs[n_ctgs]: in_lo / in_hi / g_lo / g_hi of the records come back */
+int pag_debug_trav_bounds(const pag_debug_trav_graph *g, const uint32_t *coords, uint32_t n, uint32_t *out, pag_debug_trav_contig *ctgs,
+                          uint32_t n_ctgs, int device);
+/* k_ctg_nodes: jobs[n_jobs] rows of four u64 (byte_off, out_off, len, forward) -> out[n_out].  `packed` as pag_seqs wants it
+ * (every strand on a 4-byte boundary, >= 16 readable bytes behind the last); the device copy gets the 64 bytes setup_contigs
+ * adds.  The kernel reads the 32-bit word BEHIND the one a k-mer starts in whether the k-mer reaches into it or not: for the last
+ * k-mer of the last strand that word may lie wholly behind the strand's bytes — inside the 16 bytes of pag_seqs' padding. */
+int pag_debug_ctg_nodes(const pag_debug_trav_graph *g, const uint8_t *packed, uint64_t packed_bytes, const uint64_t *jobs, uint32_t n_jobs,
+                        uint32_t max_len, uint32_t *out, uint64_t n_out, int device);
+/* the seed family.  which = 0: k_seed_first over ctgs[n_ctgs] (out: n_ctgs x stride words); 1: k_seed_window over reqs[n_req]
+ * rows of four u64 (ctg, left, right, pos) (out: n_req x TRAV_SEED_PARTS x stride words); 2: k_checkpoints over reqs (out: 3 words per
+ * request; stride is not read).  out[out_words] may be longer than that: the rest must come back as it went in. */
+int pag_debug_trav_seeds(const pag_debug_trav_graph *g, int which, const pag_debug_trav_contig *ctgs, uint32_t n_ctgs, const uint32_t *nodes,
+                         uint64_t n_node_words, const uint32_t *gbits, uint64_t n_gbits, const uint32_t *gset, uint64_t n_gset,
+                         const uint64_t *reqs, uint32_t n_req, uint64_t dev, uint32_t *out, uint64_t out_words, uint32_t stride, int device);
+/* k_pack_paths: descs[n] rows of four u64 (first entry in seq_v / seq_s / seq_x, len, word offset in out, leap job: seq_x is
+ * read) */
+int pag_debug_pack_paths(const pag_debug_trav_graph *g, const uint32_t *seq_v, const uint32_t *seq_s, const uint64_t *seq_x, uint64_t n_seq,
+                         const uint64_t *descs, uint32_t n, uint64_t max_len, uint32_t *out, uint64_t out_words, int device);
+/* k_commit of seq_v[len] into gbits + gbits_off (bitmap over [in_lo, in_hi)) and gset[ncap] */
+int pag_debug_commit(const uint32_t *seq_v, uint64_t len, uint32_t in_lo, uint32_t in_hi, uint32_t *gbits, uint64_t n_gbits, uint64_t gbits_off,
+                     uint32_t *gset, uint32_t ncap, int device);
+/* k_clear_ranges on buf[bytes], whose device copy starts on a 256-byte boundary: ranges[n] rows of three u64 (offset, bytes, word) */
+int pag_debug_clear_ranges(uint8_t *buf, uint64_t bytes, const uint64_t *ranges, uint64_t n, int device);
+/* k_concat_parts: parts[n_parts] rows of three u64 (first entry in src_v / src_s, start in out_v / out_s, n) */
+int pag_debug_concat_parts(const uint32_t *src_v, const uint32_t *src_s, uint64_t n_src, const uint64_t *parts, uint32_t n_parts, uint32_t *out_v,
+                           uint32_t *out_s, uint64_t n_out, uint32_t first_step, int device);
+/* the gathers.  which = 0: k_gather_pc (out: u32[len]); 1: k_gather_path with max_blocks (out: pag_path_node[len]); 2:
+ * k_gather_vertices over the k-mer-major ids seq_v (out: pag_path_node[len]; seq_s, max_blocks not read) */
+int pag_debug_gathers(const pag_debug_trav_graph *g, int which, const uint32_t *seq_v, const uint32_t *seq_s, uint64_t len, uint32_t max_blocks,
+                      void *out, int device);
+
 /* ---- libpagraph_host.so ---- */
 /* one record's column classes / one sequence packed, by the production path or by the scalar loop alone */
 void pagh_debug_classify_columns(const char *q, uint64_t n, const char *r, uint64_t rn, uint32_t *words, uint32_t *n_emit,

@@ -139,7 +139,7 @@ def test_signatures_agree_with_the_headers():
 
 
 def test_every_struct_of_the_headers_is_mirrored_or_excused():
-    declared = declared_structs(PUBLIC_HEADERS)
+    declared = declared_structs(ALL_HEADERS)  # (the test hooks' structs too: a mirror of one is held to its header like any other)
     assert len(declared) > 15, "the struct parser found too little"
     mirrored = set(capi.STRUCTS) | set(capi.DTYPES)
     for name in declared:

@@ -318,3 +318,27 @@ def test_walk_that_leaves_the_cut_view_is_walked_again_on_the_whole_graph(name, 
         seen[label] = r.stderr.count("a walk left the view")
     assert seen["nohalo"] > 0, "no walk left the view without halo and margin: the walk-again path did not run"
     assert seen["whole"] == 0 and seen["default"] == 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["join_rev_t16", "two_blocks_both_orient_t16"])
+def test_seed_window_searched_again_with_a_larger_stride(name, workdir):
+    """The regrow loop of reseed() (walk_session_loop.hpp): k_seed_window clips its writes at the stride it is given and reports
+    the unclipped count, and a part with more candidates than fit is searched again with a larger stride.  The first stride is
+    2 048 words per part, which no golden fills; PAG_DEBUG_SEED_STRIDE=4 leaves room for three candidates per part, so that the
+    contigs of these goldens, which re-seed with four to six candidates in a part, take the loop (the other seven goldens,
+    join_fwd_t1 among them, never have more than three in a part: measured, they print no such line).  The outputs are the
+    reference's golden bytes, and every repeated search prints its line: a run in which no part had more than three
+    candidates proves nothing and fails here."""
+    spec = goldens.load_spec(name)
+    ind = goldens.materialize_inputs(name, str(workdir / "seedstride" / name / "in"))
+    out = str(workdir / "seedstride" / name / "out")
+    os.makedirs(out, exist_ok=True)
+    argv = synth.pagraph_argv(EXE, ind, out, threads=spec["threads"], epsilon=spec["epsilon"], cov=spec["cov"])
+    r = subprocess.run(argv, capture_output=True, text=True, env=dict(os.environ, PAGRAPH_TIMING="1", PAG_DEBUG_SEED_STRIDE="4"), timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:] + r.stdout[-2000:]
+    goldens.compare_out_dir(name, out)
+    again = [(int(a), int(b)) for a, b in re.findall(r"\[timing\] seed windows: .* searched again with stride (\d+) -> (\d+)", r.stderr)]
+    print(again)
+    assert again, "no seed window had more than three candidates in a part: the search-again path did not run"
+    assert again[0][0] == 4 and all(b > a and b & (b - 1) == 0 for a, b in again)
