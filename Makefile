@@ -64,7 +64,7 @@ aligngraph2_amd/bin/pre_process: $(HOST_DIR)/pre_process_main.cpp $(HOST_DIR)/li
 
 # the consensus step after pagraph: parsing / slicing on the host, the per-part graphs on host threads or on the device (csrc/hip/k_cns.hip;
 # libpagraph_hip.so is loaded at run time, by the device backend only)
-aligngraph2_amd/bin/pa_cns: $(HOST_DIR)/pa_cns_main.cpp $(B)/host/seq_db.o $(wildcard $(HOST_DIR)/*.hpp) $(HIP_DIR)/cns_graph.hpp
+aligngraph2_amd/bin/pa_cns: $(HOST_DIR)/pa_cns_main.cpp $(B)/host/seq_db.o $(wildcard $(HOST_DIR)/*.hpp) $(HIP_DIR)/cns_graph.hpp $(HIP_DIR)/cns_rows.hpp
 	@mkdir -p aligngraph2_amd/bin
 	$(CXX) $(CXXFLAGS) -o $@ $< $(B)/host/seq_db.o -ldl -pthread
 
@@ -156,6 +156,12 @@ tests/harness/bin/libpagh_serial_layout_test.so: tests/harness/serial_layout_tes
 	$(CXX) $(CXXFLAGS) -I$(HIP_DIR) -shared -o $@ $<
 
 tests/harness/bin/serial_layout_sanitized: tests/harness/serial_layout_main.cpp $(HIP_DIR)/serial_layout.hpp
+	@mkdir -p tests/harness/bin
+	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=all -I$(HIP_DIR) -o $@ $<
+
+# pa_cns's row code (cns_rows.hpp: plain C++) against a std::string restatement of the reference, a program of its own under the
+# address and undefined-behaviour sanitizers (host code only; built and run by tests/test_cns_rows.py)
+tests/harness/bin/cns_rows_sanitized: tests/harness/cns_rows_main.cpp $(HIP_DIR)/cns_rows.hpp
 	@mkdir -p tests/harness/bin
 	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=all -I$(HIP_DIR) -o $@ $<
 

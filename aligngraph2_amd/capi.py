@@ -148,6 +148,17 @@ class CnsPart(C.Structure):
                 ("edge_cap", _u32), ("aux_cap", _u32), ("out_cap", _u32)]
 
 
+class CnsSlice(C.Structure):
+    _c_name_ = "pag_cns_slice"
+    _fields_ = [("q_off", _u64), ("t_off", _u64), ("origin_start", _u64), ("slice_start", _u64), ("slice_end", _u64),
+                ("out_off", _u64), ("n_cols", _u32), ("out_cap", _u32), ("slot", _u32), ("reserved", _u32)]
+
+
+class CnsRow(C.Structure):
+    _c_name_ = "pag_cns_row"
+    _fields_ = [("str_off", _u64), ("len", _u32), ("n_ins", _u32), ("n_edge_cols", _u32), ("flag", _u32)]
+
+
 class KmerCountResult(C.Structure):
     _c_name_ = "pag_kmer_count_result"
     _fields_ = [("min_abundance", _u64), ("n_solid", _u64), ("n_kmers_counted", _u64), ("ms_count", _f64), ("ms_select", _f64)]
@@ -168,7 +179,7 @@ class DebugTravGraph(C.Structure):
 
 
 STRUCTS = {s._c_name_: s for s in (PagSeqs, PagAlnDb, PagBuildInput, PagRawDb, PagRawInput, BuildStats, Csr, ShardSlice, Region,
-                                   SerialStats, TravelParams, TravelStats, PagSucc, CnsAln, CnsPart, KmerCountResult, TraverseStats,
+                                   SerialStats, TravelParams, TravelStats, PagSucc, CnsAln, CnsPart, CnsSlice, CnsRow, KmerCountResult, TraverseStats,
                                    DebugTravGraph)}
 
 # structs of the headers that are deliberately mirrored neither in STRUCTS nor in DTYPES: C name -> why.  (The opaque
@@ -237,6 +248,13 @@ SIGNATURES = {
     "pag_classify_columns_host": (_int, [_vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _int]),
     "pag_cns_consensus": (_int, _cns),
     "pag_cns_consensus_wave": (_int, _cns),
+    "pag_cns_normalize": (_int, [_int, _vp, _u64, _vp, _u64, _vp, _vp]),
+    "pag_cns_rows_bytes": (_u64, [_vp]),
+    "pag_cns_rows_times": (None, [_vp, _vp, _vp]),
+    "pag_cns_rows_counts": (None, [_vp, _vp, _vp]),
+    "pag_cns_rows_fetch": (_int, [_vp, _vp, _vp, _u64]),
+    "pag_cns_rows_free": (None, [_vp]),
+    "pag_cns_consensus_rows": (_int, [_int, _int, _cs, _u64, _vp, _u64, _vp, _u64, _vp, _i32, _vp, _u64, _vp, _vp, _vp]),
     "pag_kmer_count": (_int, [_vp, _int, _u32, _f64, _int, _vp, _int, _vp]),
     "pag_last_error": (_cs, []),
     "pag_device_available": (_int, []),

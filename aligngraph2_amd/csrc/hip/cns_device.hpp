@@ -12,9 +12,14 @@ namespace pagdev {
 using CnsLaunchFn = void (*)(const pagcns::Arrays &A, const pagcns::Part *parts, uint32_t n, const char *backbone, const pagcns::Aln *alns, const char *qpool,
                              const char *tpool, int min_weight, char *out, uint32_t *out_len, int32_t *part_err);
 
-// the body of pag_cns_consensus / pag_cns_consensus_wave (include/pagraph_hip.h); `who` names the entry point in errors
+// the body of pag_cns_consensus / pag_cns_consensus_wave (include/pagraph_hip.h); `who` names the entry point in errors.
+// d_qpool / d_tpool: the pools in device memory already (pag_cns_consensus_rows) — qpool / tpool are not read then
 int cns_consensus_batched(const char *who, CnsLaunchFn launch, int device, const char *backbone, uint64_t backbone_len, const pag_cns_part *parts, uint64_t n_parts,
                           const pag_cns_aln *alns, uint64_t n_alns, const char *qpool, const char *tpool, uint64_t pool_bytes, int32_t min_weight, char *out,
-                          uint64_t out_bytes, uint64_t *out_off, uint32_t *out_len, int32_t *part_err);
+                          uint64_t out_bytes, uint64_t *out_off, uint32_t *out_len, int32_t *part_err, const char *d_qpool = nullptr,
+                          const char *d_tpool = nullptr);
+// the two launchers (k_cns.hip: a lane per part; k_cns_wave.hip: a wavefront per part)
+CnsLaunchFn cns_launcher_lane();
+CnsLaunchFn cns_launcher_wave();
 
 }  // namespace pagdev

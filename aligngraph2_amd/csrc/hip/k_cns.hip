@@ -56,9 +56,11 @@ void launch_lane(const pagcns::Arrays &A, const pagcns::Part *parts, uint32_t n,
 }
 }  // namespace
 
+CnsLaunchFn cns_launcher_lane() { return launch_lane; }
+
 int cns_consensus_batched(const char *who, CnsLaunchFn launch, int device, const char *backbone, uint64_t backbone_len, const pag_cns_part *parts, uint64_t n_parts,
                           const pag_cns_aln *alns, uint64_t n_alns, const char *qpool, const char *tpool, uint64_t pool_bytes, int32_t min_weight, char *out,
-                          uint64_t out_bytes, uint64_t *out_off, uint32_t *out_len, int32_t *part_err) {
+                          uint64_t out_bytes, uint64_t *out_off, uint32_t *out_len, int32_t *part_err, const char *d_qpool, const char *d_tpool) {
     static_assert(sizeof(pag_cns_aln) == sizeof(pagcns::Aln), "pag_cns_aln is pagcns::Aln");
     if (!backbone || (!parts && n_parts) || (!alns && n_alns) || !out || !out_off || !out_len || !part_err) return PAG_EINVAL;
     int n_dev = 0;
@@ -70,16 +72,22 @@ int cns_consensus_batched(const char *who, CnsLaunchFn launch, int device, const
     PAG_HIP_TRY(hipSetDevice(device));
     // inputs
     Dev D(who);
-    char *d_bb, *d_q, *d_t, *d_out;
+    char *d_bb, *d_out;
+    const char *d_q = d_qpool, *d_t = d_tpool;
     pagcns::Aln *d_alns;
     int rc;
-    if ((rc = D.alloc(&d_bb, backbone_len + 16)) || (rc = D.alloc(&d_q, pool_bytes + 16)) || (rc = D.alloc(&d_t, pool_bytes + 16)) || (rc = D.alloc(&d_alns, n_alns + 1)) ||
-        (rc = D.alloc(&d_out, out_bytes + 16)))
-        return rc;
+    const bool pools_here = !d_qpool || !d_tpool;  // (rows that are on the device already are used where they are)
+    if (pools_here) {
+        char *q, *t;
+        if ((rc = D.alloc(&q, pool_bytes + 16)) || (rc = D.alloc(&t, pool_bytes + 16))) return rc;
+        d_q = q;
+        d_t = t;
+    }
+    if ((rc = D.alloc(&d_bb, backbone_len + 16)) || (rc = D.alloc(&d_alns, n_alns + 1)) || (rc = D.alloc(&d_out, out_bytes + 16))) return rc;
     PAG_HIP_TRY(hipMemcpy(d_bb, backbone, backbone_len, hipMemcpyHostToDevice));
-    if (pool_bytes) {
-        PAG_HIP_TRY(hipMemcpy(d_q, qpool, pool_bytes, hipMemcpyHostToDevice));
-        PAG_HIP_TRY(hipMemcpy(d_t, tpool, pool_bytes, hipMemcpyHostToDevice));
+    if (pools_here && pool_bytes) {
+        PAG_HIP_TRY(hipMemcpy(const_cast<char *>(d_q), qpool, pool_bytes, hipMemcpyHostToDevice));
+        PAG_HIP_TRY(hipMemcpy(const_cast<char *>(d_t), tpool, pool_bytes, hipMemcpyHostToDevice));
     }
     if (n_alns) PAG_HIP_TRY(hipMemcpy(d_alns, alns, n_alns * sizeof(pagcns::Aln), hipMemcpyHostToDevice));
     // output places

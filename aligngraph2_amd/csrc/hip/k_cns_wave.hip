@@ -294,6 +294,8 @@ static void launch_wave(const pagcns::Arrays &A, const pagcns::Part *parts, uint
     cns_parts_wave_kernel<<<dim3(n), dim3(PAG_WAVE), 0, 0>>>(A, parts, n, backbone, alns, qpool, tpool, min_weight, out, out_len, part_err);
 }
 
+CnsLaunchFn cns_launcher_wave() { return launch_wave; }
+
 }  // namespace pagdev
 
 extern "C" int pag_cns_consensus_wave(int device, const char *backbone, uint64_t backbone_len, const pag_cns_part *parts, uint64_t n_parts, const pag_cns_aln *alns,

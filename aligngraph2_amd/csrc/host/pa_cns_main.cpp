@@ -10,8 +10,14 @@
 // csrc/hip/k_cns_wave.hip); both fail without a gfx950 device, there is no silent fallback; `flat` — the device's code
 // (csrc/hip/cns_graph.hpp: flat arrays, linked edge lists) compiled for the host, on host threads; `host` — the restatement on
 // std::vector / std::map below (AlnGraph), host code like the reference's, what the CPU tests pin on the goldens.  `auto` (the
-// default) picks `hip` from kDevicePartsMin parts on and `flat` below.  Reading, slicing, gap normalisation, the per-part sort
-// and the weights are host code in every case.
+// default) picks `hip` from kDevicePartsMin parts on and `flat` below.
+//
+// Where the rows come from (PA_CNS_INGEST): `host` (the default) — readFromRefFile below, one thread, std::string, the
+// restatement the CPU tests hold to the reference; `flat` — the file mapped and indexed (line_index.hpp), the headers parsed on
+// a thread pool, the per-part lists sorted, cut to -k and weighted from the scores alone, and only the kept slices cut and
+// gap-normalised, by csrc/hip/cns_rows.hpp on host threads, straight into the two pools; `device` — the same, the kept slices
+// normalised on the device (pag_cns_normalize, csrc/hip/k_cns_rows.hip) where the graph kernels read them next.  A file with a
+// record that is not regular (ingestParallel below) goes through `host`: that is where the reference's arithmetic wraps.
 //
 // What has to be reproduced beyond the arithmetic, because it decides ties:
 //   * the graph is boost::adjacency_list<vecS, vecS, bidirectionalS>: out- and in-edge lists are vectors in insertion order,
@@ -34,14 +40,18 @@
 #include <fstream>
 #include <iostream>
 #include <map>
+#include <memory>
 #include <queue>
 #include <sstream>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../hip/cns_graph.hpp"
+#include "../hip/cns_rows.hpp"
 #include "host_threads.hpp"
+#include "line_index.hpp"
 #include "pagraph_hip.h"
 #include "seq_db.hpp"
 
@@ -596,26 +606,51 @@ Options parseCli(int argc, char **argv) {
 // parts from which the default backend is the device (PA_CNS_BACKEND=auto)
 constexpr std::size_t kDevicePartsMin = 4096;
 
-// libpagraph_hip.so, loaded on demand from beside the executable (bin/../libpagraph_hip.so) or the loader's search path
+// libpagraph_hip.so, loaded on demand from beside the executable (<dir of /proc/self/exe>/../libpagraph_hip.so: where the program
+// IS, whatever it was called as and whatever the working directory) or the loader's search path
 struct HipLibrary {
     using ConsensusFn = int (*)(int, const char *, std::uint64_t, const pag_cns_part *, std::uint64_t, const pag_cns_aln *, std::uint64_t, const char *, const char *,
                                 std::uint64_t, std::int32_t, char *, std::uint64_t, std::uint64_t *, std::uint32_t *, std::int32_t *);
+    using ConsensusRowsFn = int (*)(int, int, const char *, std::uint64_t, const pag_cns_part *, std::uint64_t, const pag_cns_aln *, std::uint64_t, const pag_cns_rows *,
+                                    std::int32_t, char *, std::uint64_t, std::uint64_t *, std::uint32_t *, std::int32_t *);
+    using NormalizeFn = int (*)(int, const char *, std::uint64_t, const pag_cns_slice *, std::uint64_t, pag_cns_row *, pag_cns_rows **);
     using ErrorFn = const char *(*)();
     void *handle = nullptr;
     ConsensusFn consensus = nullptr, consensus_wave = nullptr;
+    ConsensusRowsFn consensus_rows = nullptr;
+    NormalizeFn normalize = nullptr;
+    std::uint64_t (*rows_bytes)(const pag_cns_rows *) = nullptr;
+    void (*rows_times)(const pag_cns_rows *, double *, double *) = nullptr;
+    void (*rows_counts)(const pag_cns_rows *, std::uint64_t *, std::uint64_t *) = nullptr;
+    int (*rows_fetch)(const pag_cns_rows *, char *, char *, std::uint64_t) = nullptr;
+    void (*rows_free)(pag_cns_rows *) = nullptr;
+    int (*device_available)() = nullptr;
     ErrorFn last_error = nullptr;
-    explicit HipLibrary(const char *argv0) {
-        std::string dir = argv0 ? argv0 : "";
-        const std::size_t slash = dir.rfind('/');
-        dir = slash == std::string::npos ? std::string(".") : dir.substr(0, slash);
-        const std::string beside = dir + "/../libpagraph_hip.so";
-        handle = dlopen(beside.c_str(), RTLD_NOW | RTLD_LOCAL);
+    HipLibrary() {
+        char exe[4096];
+        const ssize_t n = ::readlink("/proc/self/exe", exe, sizeof exe - 1);
+        if (n > 0) {
+            std::string dir(exe, static_cast<std::size_t>(n));
+            const std::size_t slash = dir.rfind('/');
+            if (slash != std::string::npos) handle = dlopen((dir.substr(0, slash) + "/../libpagraph_hip.so").c_str(), RTLD_NOW | RTLD_LOCAL);
+        }
         if (!handle) handle = dlopen("libpagraph_hip.so", RTLD_NOW | RTLD_LOCAL);
         if (!handle) throw std::runtime_error(std::string("the device backend needs libpagraph_hip.so: ") + dlerror());
-        consensus = reinterpret_cast<ConsensusFn>(dlsym(handle, "pag_cns_consensus"));
-        consensus_wave = reinterpret_cast<ConsensusFn>(dlsym(handle, "pag_cns_consensus_wave"));
-        last_error = reinterpret_cast<ErrorFn>(dlsym(handle, "pag_last_error"));
-        if (!consensus || !consensus_wave || !last_error) throw std::runtime_error("libpagraph_hip.so does not export pag_cns_consensus / pag_cns_consensus_wave");
+        const auto sym = [&](auto &fn, const char *name) {
+            fn = reinterpret_cast<std::remove_reference_t<decltype(fn)>>(dlsym(handle, name));
+            if (!fn) throw std::runtime_error(std::string("libpagraph_hip.so does not export ") + name);
+        };
+        sym(consensus, "pag_cns_consensus");
+        sym(consensus_wave, "pag_cns_consensus_wave");
+        sym(consensus_rows, "pag_cns_consensus_rows");
+        sym(normalize, "pag_cns_normalize");
+        sym(rows_bytes, "pag_cns_rows_bytes");
+        sym(rows_times, "pag_cns_rows_times");
+        sym(rows_counts, "pag_cns_rows_counts");
+        sym(rows_fetch, "pag_cns_rows_fetch");
+        sym(rows_free, "pag_cns_rows_free");
+        sym(device_available, "pag_device_available");
+        sym(last_error, "pag_last_error");
     }
     HipLibrary(const HipLibrary &) = delete;
     HipLibrary &operator=(const HipLibrary &) = delete;
@@ -623,6 +658,221 @@ struct HipLibrary {
         if (handle) dlclose(handle);
     }
 };
+
+// ---------------------------------------------------------------------------------------------------------------------
+// PA_CNS_INGEST=flat / device: the rows without readFromRefFile
+// ---------------------------------------------------------------------------------------------------------------------
+struct Ingested {
+    std::vector<pag_cns_aln> flat;               // the kept alignments of all parts, part after part, in final (sorted) order
+    std::vector<std::uint64_t> partFirst;        // part i's are flat[partFirst[i] .. partFirst[i + 1])
+    std::vector<std::uint64_t> nIns, nEdgeCols;  // per part: what sizes its graph
+    std::unique_ptr<char, decltype(&std::free)> qpool{nullptr, &std::free}, tpool{nullptr, &std::free};  // `flat`
+    std::uint64_t poolBytes = 0;
+    pag_cns_rows *dev = nullptr;                 // `device`
+    double sIndex = 0, sHeaders = 0, sLists = 0, sRows = 0, sUpload = 0;
+    std::uint64_t nPieces = 0, nOversize = 0;    // `device`: pieces the text went up in, slices normalised on the host after all
+};
+
+// AlignData::weightAln on the scores alone
+std::vector<std::size_t> weightScores(const std::vector<unsigned> &scores, std::size_t alpha) {
+    if (scores.empty()) return {};
+    unsigned maxScore = scores[0], minScore = scores[0];
+    for (unsigned sc : scores) {
+        maxScore = std::max(maxScore, sc);
+        minScore = std::min(minScore, sc);
+    }
+    const unsigned scoreRange = maxScore - minScore;
+    std::vector<std::size_t> weights;
+    weights.reserve(scores.size());
+    for (unsigned sc : scores) weights.push_back(std::max(static_cast<std::size_t>((sc - minScore) * 1.0 / std::max(scoreRange, 1U) * alpha), std::size_t(1)));
+    return weights;
+}
+
+// Returns false, with the reason, when a record is not REGULAR: the file then goes through readFromRefFile.  Regular: the header
+// parsed, 0 < refEnd, refBegin < refEnd, both rows of the same length and under 2^31 columns, every slice at least one column.
+// Everything else is where the reference's arithmetic wraps (an all-zero record after a malformed header) or where its
+// behaviour is undefined (the len - 1 of an empty slice); the goldens pin the std::string code there.
+bool ingestParallel(const std::string &path, const std::string &skeleton, std::size_t partLen, std::size_t topK, std::size_t alpha, HipLibrary *hip, int device,
+                    Ingested &out, std::string &why) {
+    using Clock = std::chrono::steady_clock;
+    const auto lap = [](Clock::time_point &t) {
+        const auto now = Clock::now();
+        const double s = std::chrono::duration<double>(now - t).count();
+        t = now;
+        return s;
+    };
+    auto t = Clock::now();
+    if (skeleton.empty() || partLen == 0) {
+        why = "no backbone";
+        return false;
+    }
+    const std::size_t partNum = (skeleton.size() + partLen - 1) / partLen;
+    pagh::FileLines lines;
+    const bool opened = lines.load(path);  // (a file that cannot be opened holds no record, AlignData.cpp:36-43)
+    const std::size_t nRec = opened ? lines.size() / 3 : 0;  // record r is lines 3r, 3r + 1, 3r + 2; a trailing partial record is dropped
+    out.sIndex = lap(t);
+
+    // the headers: the same ten stream extractions, one stringstream per thread
+    struct Rec {
+        std::uint64_t begin, end;
+        unsigned score;
+        std::uint32_t nSlices;
+    };
+    std::vector<Rec> recs(nRec);
+    std::atomic<std::size_t> firstBad(SIZE_MAX);
+    const auto bad = [&](std::size_t r) {
+        std::size_t cur = firstBad.load();
+        while (r < cur && !firstBad.compare_exchange_weak(cur, r)) {
+        }
+    };
+    constexpr std::size_t kGrain = 2048;
+    pagh::parallelFor((nRec + kGrain - 1) / kGrain, 1, [&](std::size_t c) {
+        std::stringstream ss;
+        std::string queryName, refName, forward, score;
+        for (std::size_t r = c * kGrain, e = std::min(nRec, r + kGrain); r < e; ++r) {
+            std::size_t queryBegin = 0, queryEnd = 0, querySize = 0, refBegin = 0, refEnd = 0, refSize = 0;
+            ss.clear();
+            ss.str(lines.str(3 * r));
+            ss >> queryName >> refName >> forward >> score >> queryBegin >> queryEnd >> querySize >> refBegin >> refEnd >> refSize;
+            Rec &R = recs[r];
+            R = Rec{refBegin, refEnd, 0, 0};
+            if (ss.fail() || refEnd == 0 || refBegin >= refEnd || lines.length(3 * r + 1) != lines.length(3 * r + 2) || lines.length(3 * r + 2) >= 0x80000000ull) {
+                bad(r);
+                continue;
+            }
+            R.score = static_cast<unsigned>(std::atoi(score.c_str()));
+            const std::size_t leftPart = refBegin / partLen, rightPart = std::min((refEnd - 1) / partLen, partNum - 1);
+            R.nSlices = rightPart >= leftPart ? static_cast<std::uint32_t>(std::min<std::size_t>(rightPart - leftPart + 1, 0xFFFFFFFFu)) : 0;
+        }
+    });
+    if (firstBad.load() != SIZE_MAX) {
+        why = "record " + std::to_string(firstBad.load()) + " is not regular (its header or the lengths of its rows)";
+        return false;
+    }
+    std::vector<std::uint64_t> sliceFirst(nRec + 1, 0);
+    for (std::size_t r = 0; r < nRec; ++r) sliceFirst[r + 1] = sliceFirst[r] + recs[r].nSlices;
+    const std::uint64_t nSlicesAll = sliceFirst[nRec];
+    std::vector<std::uint32_t> sliceCols(nSlicesAll);  // every slice's columns: the slot it needs, and no slice may be empty
+    const auto sliceOf = [&](std::size_t r, std::size_t part) {
+        pag_cns_slice S{};
+        S.q_off = lines.offset(3 * r + 1);
+        S.t_off = lines.offset(3 * r + 2);
+        S.origin_start = recs[r].begin;
+        S.slice_start = part * partLen;
+        S.slice_end = std::min((part + 1) * partLen, skeleton.size());
+        S.n_cols = static_cast<std::uint32_t>(lines.length(3 * r + 2));
+        return S;
+    };
+    pagh::parallelFor((nRec + kGrain - 1) / kGrain, 1, [&](std::size_t c) {
+        for (std::size_t r = c * kGrain, e = std::min(nRec, r + kGrain); r < e; ++r) {
+            const std::size_t leftPart = recs[r].begin / partLen;
+            for (std::uint32_t k = 0; k < recs[r].nSlices; ++k) {
+                const pag_cns_slice S = sliceOf(r, leftPart + k);
+                std::uint32_t left, right;
+                pagrows::slice_bounds(lines.base() + S.t_off, S.n_cols, S.origin_start, S.slice_start, S.slice_end, &left, &right);
+                sliceCols[sliceFirst[r] + k] = right - left;
+                if (right == left) bad(r);
+            }
+        }
+    });
+    if (firstBad.load() != SIZE_MAX) {
+        why = "record " + std::to_string(firstBad.load()) + " is not regular (a slice of it has no column)";
+        return false;
+    }
+    out.sHeaders = lap(t);
+
+    // every part's list in file order, then per part the same proxy std::sort as the host ingest, the cut to -k and the weights:
+    // all from the scores, before any row is normalised (a slice's rows depend on nothing else, so cutting first changes nothing)
+    struct Cand {
+        unsigned score;
+        std::uint32_t k;  // slice k of ...
+        std::uint64_t rec;
+    };
+    std::vector<std::vector<Cand>> lists(partNum);
+    for (std::size_t r = 0; r < nRec; ++r) {
+        const std::size_t leftPart = recs[r].begin / partLen;
+        for (std::uint32_t k = 0; k < recs[r].nSlices; ++k) lists[leftPart + k].push_back(Cand{recs[r].score, k, r});
+    }
+    std::vector<std::vector<std::size_t>> weights(partNum);
+    pagh::parallelFor(partNum, 1, [&](std::size_t i) {
+        auto &lst = lists[i];
+        struct Proxy {
+            unsigned score;
+            std::size_t idx;
+        };
+        std::vector<Proxy> proxy(lst.size());
+        for (std::size_t x = 0; x < lst.size(); ++x) proxy[x] = Proxy{lst[x].score, x};
+        std::sort(proxy.begin(), proxy.end(), [](const Proxy &l, const Proxy &r) { return l.score > r.score; });
+        std::vector<Cand> kept;
+        std::vector<unsigned> scores;
+        kept.reserve(std::min(lst.size(), topK));
+        for (std::size_t x = 0; x < proxy.size() && x < topK; ++x) kept.push_back(lst[proxy[x].idx]);
+        for (const Cand &c : kept) scores.push_back(c.score);
+        lst.swap(kept);
+        weights[i] = weightScores(scores, alpha);
+    });
+    out.partFirst.assign(partNum + 1, 0);
+    for (std::size_t i = 0; i < partNum; ++i) out.partFirst[i + 1] = out.partFirst[i] + lists[i].size();
+    const std::uint64_t nKept = out.partFirst[partNum];
+    if (nKept >= 0xFFFFFFFFull) throw std::runtime_error("pa_cns: more than 2^32 kept alignments");
+    out.flat.assign(nKept, pag_cns_aln{});
+    std::vector<pag_cns_slice> slices(nKept);
+    std::uint64_t poolBytes = 0;
+    for (std::size_t i = 0; i < partNum; ++i)
+        for (std::size_t x = 0; x < lists[i].size(); ++x) {
+            const Cand &c = lists[i][x];
+            const std::uint64_t slot = out.partFirst[i] + x;
+            const std::size_t leftPart = recs[c.rec].begin / partLen;
+            pag_cns_slice S = sliceOf(c.rec, i);
+            S.slot = static_cast<std::uint32_t>(slot);
+            S.out_off = poolBytes;
+            S.out_cap = 2 * sliceCols[sliceFirst[c.rec] + c.k];  // (every column can become two; columns < 2^31 / 2 or the graph stage refuses the part anyway)
+            if (sliceCols[sliceFirst[c.rec] + c.k] > 0x7FFFFFFFu) throw std::runtime_error("pa_cns: a slice with more than 2^31 columns");
+            poolBytes += S.out_cap;
+            slices[slot] = S;
+            pag_cns_aln &f = out.flat[slot];
+            f.start = static_cast<std::uint32_t>(i == leftPart ? recs[c.rec].begin - leftPart * partLen + 1 : 1);
+            f.weight = static_cast<std::int32_t>(weights[i][x]);
+        }
+    out.poolBytes = poolBytes;
+    std::vector<std::vector<Cand>>().swap(lists);
+    out.sLists = lap(t);
+
+    // the rows of the kept slices
+    std::vector<pag_cns_row> rows(nKept);
+    if (!hip) {
+        out.qpool.reset(static_cast<char *>(std::malloc(poolBytes + 64)));
+        out.tpool.reset(static_cast<char *>(std::malloc(poolBytes + 64)));
+        if (!out.qpool || !out.tpool) throw std::runtime_error("pa_cns: out of memory for the row pools");
+        static_assert(sizeof(pag_cns_slice) == sizeof(pagrows::Slice) && sizeof(pag_cns_row) == sizeof(pagrows::Row), "pag_cns_slice / pag_cns_row are pagrows::Slice / Row");
+        pagh::parallelFor(nKept, 64, [&](std::size_t s) {
+            pagrows::Slice S;
+            std::memcpy(&S, &slices[s], sizeof S);
+            const pagrows::Row R = pagrows::run_slice(lines.base(), S, nullptr, nullptr, 1, 0, out.qpool.get(), out.tpool.get());
+            std::memcpy(&rows[s], &R, sizeof R);
+        });
+        out.sRows = lap(t);
+    } else {
+        // in text order: the text goes up in pieces with their slices
+        std::sort(slices.begin(), slices.end(), [](const pag_cns_slice &l, const pag_cns_slice &r) { return l.q_off != r.q_off ? l.q_off < r.q_off : l.slot < r.slot; });
+        const int rc = hip->normalize(device, lines.base(), lines.bytes(), slices.data(), nKept, rows.data(), &out.dev);
+        if (rc != 0) throw std::runtime_error("pag_cns_normalize failed (" + std::to_string(rc) + "): " + hip->last_error());
+        hip->rows_times(out.dev, &out.sUpload, nullptr);
+        hip->rows_counts(out.dev, &out.nPieces, &out.nOversize);
+        out.sRows = lap(t) - out.sUpload;
+    }
+    out.nIns.assign(partNum, 0);
+    out.nEdgeCols.assign(partNum, 0);
+    for (std::size_t i = 0; i < partNum; ++i)
+        for (std::uint64_t s = out.partFirst[i]; s < out.partFirst[i + 1]; ++s) {
+            if (rows[s].flag != 0) throw std::runtime_error("pa_cns: a slice did not fit its slot");
+            out.flat[s].str_off = rows[s].str_off;
+            out.flat[s].len = rows[s].len;
+            out.nIns[i] += rows[s].n_ins;
+            out.nEdgeCols[i] += rows[s].n_edge_cols;
+        }
+    return true;
+}
 
 int main(int argc, char **argv) {
     if (argc <= 1) {
@@ -656,7 +906,50 @@ int main(int argc, char **argv) {
         const std::size_t partNum = (backbone.size() + partLen - 1) / partLen;
         std::cout << "PartNum=" << partNum << std::endl;
         std::vector<std::string> consensusResults(partNum);
-        auto alignments = readFromRefFile(opt.align, backbone, partLen);
+        const char *backendEnv = std::getenv("PA_CNS_BACKEND");
+        std::string backend = backendEnv ? backendEnv : "auto";
+        if (backend == "auto") backend = partNum >= kDevicePartsMin ? "hip" : "flat";
+        if (backend != "hip" && backend != "wave" && backend != "flat" && backend != "host")
+            throw std::runtime_error("PA_CNS_BACKEND must be hip, wave, flat, host or auto");
+        const bool stageTimes = pagh::envInt("PA_CNS_STAGE_TIMES", 0) != 0;
+        using Clock = std::chrono::steady_clock;
+        const auto seconds = [](Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
+        // Where the rows come from (the head of this file).  flat and device hand the graph stage flat arrays, so they need a
+        // backend that takes them; device leaves the rows on the device, so it needs one that runs there.  No fallback to
+        // another mode — but a file with a record that is not regular is read by the host ingest, whatever the mode.
+        const char *ingestEnv = std::getenv("PA_CNS_INGEST");
+        const std::string ingest = ingestEnv ? ingestEnv : "host";
+        if (ingest != "host" && ingest != "flat" && ingest != "device") throw std::runtime_error("PA_CNS_INGEST must be host, flat or device");
+        if (ingest != "host" && backend == "host")
+            throw std::runtime_error("PA_CNS_INGEST=" + ingest + " needs a graph backend that takes flat rows: PA_CNS_BACKEND=hip, wave or flat, not host");
+        if (ingest == "device" && backend != "hip" && backend != "wave")
+            throw std::runtime_error("PA_CNS_INGEST=device leaves the rows on the device: it needs PA_CNS_BACKEND=hip or wave, not " + backend);
+        const int device = static_cast<int>(pagh::envInt("PAGRAPH_DEVICE", 0));
+        std::unique_ptr<HipLibrary> hip;  // (loaded when, and only when, something runs on the device)
+        Ingested ing;
+        bool ingested = false;
+        const auto tIngest = Clock::now();
+        if (ingest != "host") {
+            if (ingest == "device") {
+                hip.reset(new HipLibrary());
+                if (hip->device_available() == 0)
+                    throw std::runtime_error("PA_CNS_INGEST=device: no gfx950 device (pag_cns_normalize runs there; PA_CNS_INGEST=flat makes the rows on host threads)");
+            }
+            std::string why;
+            ingested = ingestParallel(opt.align, backbone, partLen, opt.topK, opt.alpha, hip.get(), device, ing, why);
+            if (!ingested && stageTimes) std::cerr << "pa_cns: ingest (" << ingest << ") falls back to the host ingest: " << why << std::endl;
+        }
+        auto alignments = ingested ? std::vector<std::vector<ScoredAln>>(partNum) : readFromRefFile(opt.align, backbone, partLen);
+        const double sRead = seconds(tIngest, Clock::now());
+        const char *dumpRows = std::getenv("PA_CNS_DUMP_ROWS");
+        std::vector<std::string> dumpText(dumpRows ? partNum : 0);  // PA_CNS_DUMP_ROWS with the host backend: the parts' lines as they are built
+        const auto dumpLine = [](std::string &to, std::size_t part, std::uint32_t start, long long weight, const char *q, const char *t, std::size_t len) {
+            to += std::to_string(part) + ' ' + std::to_string(start) + ' ' + std::to_string(weight) + ' ';
+            to.append(q, len);
+            to += ' ';
+            to.append(t, len);
+            to += '\n';
+        };
         std::atomic<std::size_t> consensusLen(0), next(0);
         std::atomic<bool> failed(false);
         std::string failure;
@@ -666,19 +959,11 @@ int main(int argc, char **argv) {
         // (csrc/hip/cns_graph.hpp) on host threads; host: the std::vector / std::map restatement.  Default: by the number of parts —
         // a part is a serial chain of dependent accesses, the device wins by running thousands side by side, host threads win on
         // the few hundred parts of one contig of the pipeline (AlignGraph2.py:503 calls pa_cns once per new contig;
-        // profiles/r06_pa_cns_timing.json).
-        const char *backendEnv = std::getenv("PA_CNS_BACKEND");
-        std::string backend = backendEnv ? backendEnv : "auto";
-        if (backend == "auto") backend = partNum >= kDevicePartsMin ? "hip" : "flat";
-        if (backend != "hip" && backend != "wave" && backend != "flat" && backend != "host")
-            throw std::runtime_error("PA_CNS_BACKEND must be hip, wave, flat, host or auto");
+        // profiles/r06_pa_cns_timing.json).  (The backend is chosen above, before the rows are read.)
         const bool onHost = backend == "host";
         // PA_CNS_STAGE_TIMES=1: the graph stage's seconds on stderr (a host clock around the backend call, which ends in a device
         // synchronise; `host` builds its graphs inside the per-part sort, so its figure holds the sort too) and, for `flat`, the
-        // thread-seconds of its three phases
-        const bool stageTimes = pagh::envInt("PA_CNS_STAGE_TIMES", 0) != 0;
-        using Clock = std::chrono::steady_clock;
-        const auto seconds = [](Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
+        // thread-seconds of its three phases; and the ingest's seconds by step
         const auto tSort = Clock::now();
         std::vector<std::vector<std::size_t>> partWeights(partNum);
         auto work = [&]() {
@@ -702,6 +987,10 @@ int main(int argc, char **argv) {
                     partWeights[i] = weightAln(alns, opt.alpha);
                     if (!onHost) continue;  // (the graphs of all parts are built together below)
                     const auto &weights = partWeights[i];
+                    if (dumpRows)
+                        for (std::size_t x = 0; x < weights.size(); ++x)
+                            dumpLine(dumpText[i], i, alns[x].aln.start, static_cast<std::int32_t>(weights[x]), alns[x].aln.qstr.data(), alns[x].aln.tstr.data(),
+                                     alns[x].aln.qstr.size());
                     AlnGraph g(backbone.substr(left, right - left));
                     for (std::size_t x = 0; x < weights.size(); ++x) g.addAln(alns[x].aln, static_cast<int>(weights[x]));
                     g.mergeNodes();
@@ -721,7 +1010,17 @@ int main(int argc, char **argv) {
             for (auto &t : pool) t.join();
         }
         if (failed) throw std::runtime_error(failure);
+        const double sSort = seconds(tSort, Clock::now());
         if (stageTimes && onHost) std::cerr << "pa_cns: graph stage (host, with the per-part sort) " << seconds(tSort, Clock::now()) << " s" << std::endl;
+        // the ingest by step.  The host ingest does not split: reading, slicing and normalising are one loop (under `rows`), the
+        // per-part sort and the weights come after it (under `lists`; with the host backend the graphs are built in there too)
+        if (stageTimes && !ingested)
+            std::cerr << "pa_cns: ingest (host) index 0 headers 0 lists " << sSort << " rows " << sRead << " upload 0" << std::endl;
+        if (stageTimes && ingested)
+            std::cerr << "pa_cns: ingest (" << ingest << ") index " << ing.sIndex << " headers " << ing.sHeaders << " lists " << ing.sLists << " rows " << ing.sRows
+                      << " upload " << ing.sUpload << std::endl;
+        if (stageTimes && ingested && ingest == "device")
+            std::cerr << "pa_cns: rows on the device: " << ing.partFirst[partNum] << " slices, " << ing.nPieces << " pieces, " << ing.nOversize << " oversize" << std::endl;
         if (!onHost) {
             // the parts as flat arrays: every alignment's two rows in two pools, the regions of every part's graph sized from its
             // columns (include/pagraph_hip.h, pag_cns_consensus)
@@ -734,10 +1033,10 @@ int main(int argc, char **argv) {
                 pag_cns_part &P = parts[i];
                 P.bb_off = left;
                 P.bb_len = static_cast<std::uint32_t>(right - left);
-                P.aln_first = flat.size();
-                std::uint64_t nIns = 0, nEdgeCols = 0;
+                P.aln_first = ingested ? ing.partFirst[i] : flat.size();
+                std::uint64_t nIns = ingested ? ing.nIns[i] : 0, nEdgeCols = ingested ? ing.nEdgeCols[i] : 0;
                 const auto &alns = alignments[i];
-                for (std::size_t x = 0; x < partWeights[i].size(); ++x) {
+                for (std::size_t x = 0; x < partWeights[i].size(); ++x) {  // (no list here when the rows are in the pools already)
                     const Aln &a = alns[x].aln;
                     pag_cns_aln f{};
                     f.str_off = qpool.size();
@@ -754,7 +1053,7 @@ int main(int argc, char **argv) {
                     }
                 }
                 std::vector<ScoredAln>().swap(alignments[i]);  // (its rows live in the pools now)
-                P.n_aln = static_cast<std::uint32_t>(flat.size() - P.aln_first);
+                P.n_aln = static_cast<std::uint32_t>(ingested ? ing.partFirst[i + 1] - ing.partFirst[i] : flat.size() - P.aln_first);
                 const std::uint64_t nodeCap = P.bb_len + 2ull + nIns, edgeCap = P.bb_len + 1ull + nEdgeCols + P.n_aln + 4096ull;
                 if (nodeCap > 0x7FFFFFFFull || edgeCap > 0x7FFFFFFFull) throw std::runtime_error("pa_cns: a part with more than 2^31 graph slots");
                 P.node_cap = static_cast<std::uint32_t>(nodeCap);
@@ -763,6 +1062,23 @@ int main(int argc, char **argv) {
                 P.out_cap = P.node_cap;
                 outBytes += P.out_cap;
             }
+            if (ingested) flat.swap(ing.flat);
+            const char *qrows = ingested ? ing.qpool.get() : qpool.data(), *trows = ingested ? ing.tpool.get() : tpool.data();  // (null: the rows are on the device)
+            const std::uint64_t poolBytes = ingested ? ing.poolBytes : qpool.size();
+            if (dumpRows) {
+                std::vector<char> fq, ft;
+                if (ingested && ing.dev) {  // (a verification aid: the rows come back for the dump alone)
+                    fq.resize(poolBytes + 1);
+                    ft.resize(poolBytes + 1);
+                    const int rc = hip->rows_fetch(ing.dev, fq.data(), ft.data(), poolBytes);
+                    if (rc != 0) throw std::runtime_error("pag_cns_rows_fetch failed (" + std::to_string(rc) + "): " + hip->last_error());
+                }
+                const char *dq = ing.dev ? fq.data() : qrows, *dt = ing.dev ? ft.data() : trows;
+                pagh::parallelFor(partNum, 1, [&](std::size_t i) {
+                    for (std::uint64_t a = parts[i].aln_first; a < parts[i].aln_first + parts[i].n_aln; ++a)
+                        dumpLine(dumpText[i], i, flat[a].start, flat[a].weight, dq + flat[a].str_off, dt + flat[a].str_off, flat[a].len);
+                });
+            }
             std::vector<char> outBuf(outBytes + 16);
             std::vector<std::uint64_t> outOff(partNum + 1, 0);
             std::vector<std::uint32_t> outLen(partNum, 0);
@@ -770,19 +1086,25 @@ int main(int argc, char **argv) {
             std::atomic<long long> phaseNs[3] = {{0}, {0}, {0}};  // flat under PA_CNS_STAGE_TIMES: add_aln, merge_nodes, best_path + trim
             auto tGraph = Clock::now();
             if (backend == "hip" || backend == "wave") {
-                const int device = static_cast<int>(pagh::envInt("PAGRAPH_DEVICE", 0));
-                const HipLibrary hip(argv[0]);  // (throws when the library or a gfx950 device is missing: there is no silent fallback)
+                if (!hip) hip.reset(new HipLibrary());  // (throws when the library is missing; the call fails without a gfx950 device: there is no silent fallback)
                 const bool wave = backend == "wave";
                 if (stageTimes) {  // (the HIP runtime's start and the code object's load stay out of the stage's clock)
-                    const auto available = reinterpret_cast<int (*)()>(dlsym(hip.handle, "pag_device_available"));
-                    if (available) (void)available();
+                    (void)hip->device_available();
                     tGraph = Clock::now();
                 }
-                const int rc = (wave ? hip.consensus_wave : hip.consensus)(device, backbone.data(), backbone.size(), parts.data(), partNum, flat.data(), flat.size(),
-                                                                           qpool.data(), tpool.data(), qpool.size(), 0, outBuf.data(), outBytes, outOff.data(),
-                                                                           outLen.data(), partErr.data());
+                const bool onDevice = ingested && ing.dev;  // (the rows are where the kernels read them: no pool is uploaded)
+                const int rc = onDevice ? hip->consensus_rows(device, wave ? 1 : 0, backbone.data(), backbone.size(), parts.data(), partNum, flat.data(), flat.size(), ing.dev,
+                                                              0, outBuf.data(), outBytes, outOff.data(), outLen.data(), partErr.data())
+                                        : (wave ? hip->consensus_wave : hip->consensus)(device, backbone.data(), backbone.size(), parts.data(), partNum, flat.data(),
+                                                                                        flat.size(), qrows, trows, poolBytes, 0, outBuf.data(), outBytes, outOff.data(),
+                                                                                        outLen.data(), partErr.data());
+                if (ing.dev) {
+                    hip->rows_free(ing.dev);
+                    ing.dev = nullptr;
+                }
                 if (rc != 0)
-                    throw std::runtime_error(std::string(wave ? "pag_cns_consensus_wave" : "pag_cns_consensus") + " failed (" + std::to_string(rc) + "): " + hip.last_error());
+                    throw std::runtime_error(std::string(onDevice ? "pag_cns_consensus_rows" : wave ? "pag_cns_consensus_wave" : "pag_cns_consensus") + " failed (" +
+                                             std::to_string(rc) + "): " + hip->last_error());
             } else {  // the device's code on host threads
                 std::uint64_t oo = 0;
                 for (std::size_t i = 0; i < partNum; ++i) {
@@ -817,7 +1139,7 @@ int main(int argc, char **argv) {
                         std::uint32_t len = 0;
                         const auto *fa = reinterpret_cast<const pagcns::Aln *>(flat.data());
                         if (!stageTimes) {
-                            partErr[i] = pagcns::run_part(A, P, backbone.data(), fa, qpool.data(), tpool.data(), 0, outBuf.data(), &len);
+                            partErr[i] = pagcns::run_part(A, P, backbone.data(), fa, qrows, trows, 0, outBuf.data(), &len);
                         } else {  // run_part's steps with a clock between them
                             pagcns::Graph g;
                             pagcns::bind(g, A, P);
@@ -825,7 +1147,7 @@ int main(int argc, char **argv) {
                             pagcns::init_backbone(g, backbone.data() + P.bb_off, P.bb_len);
                             for (std::uint32_t a = 0; a < P.n_aln && !g.err; ++a) {
                                 const pagcns::Aln &al = fa[P.aln_first + a];
-                                pagcns::add_aln(g, qpool.data() + al.str_off, tpool.data() + al.str_off, al.len, al.start, al.weight);
+                                pagcns::add_aln(g, qrows + al.str_off, trows + al.str_off, al.len, al.start, al.weight);
                             }
                             const auto t1 = Clock::now();
                             if (!g.err) pagcns::merge_nodes(g);
@@ -857,6 +1179,11 @@ int main(int argc, char **argv) {
                 consensusResults[i].assign(outBuf.data() + outOff[i], outLen[i]);
                 consensusLen += outLen[i];
             }
+        }
+        if (dumpRows) {  // part start weight qrow trow, a line per kept alignment, parts in order, alignments in final order
+            std::ofstream df(dumpRows);
+            for (const std::string &t : dumpText) df << t;
+            if (!df) throw std::runtime_error(std::string("PA_CNS_DUMP_ROWS: cannot write ") + dumpRows);
         }
         std::cout << consensusLen << std::endl;
         std::cout << backbone.size() << std::endl;

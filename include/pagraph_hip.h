@@ -570,6 +570,48 @@ int pag_cns_consensus_wave(int device, const char *backbone, uint64_t backbone_l
                            int32_t min_weight, char *out, uint64_t out_bytes, uint64_t *out_off, uint32_t *out_len,
                            int32_t *part_err);
 
+/* The rows themselves made on the device (csrc/hip/k_cns_rows.hip over csrc/hip/cns_rows.hpp): `text` is the 3-line ALN file in
+ * HOST memory; every slice names the two rows of its record in it, the record's backbone start and the part's backbone interval.
+ * A slice is cut as AlignData::sliceHelper cuts it (AlignData.cpp:11-34) and gap-normalised as dagcon's normalizeGaps does
+ * (cns/Alignment.cpp:131-217) into its slot [out_off, out_off + out_cap) of two DEVICE pools the call allocates; out_cap must be
+ * at least twice the slice's columns (PAG_ERANGE otherwise), slots must not overlap.  The slices are in text order (q_off not
+ * decreasing): the text goes up in pieces, with their slices, so that device memory stays under free memory x 0.8.  A slice
+ * with more columns than the kernel's work rows hold is normalised by the same code on the host and its rows are uploaded into
+ * its slot.  rows[slice.slot] (host memory, n_slices entries) tells where the rows are and what sizes a part's graph. */
+typedef struct pag_cns_slice {
+    uint64_t q_off, t_off;           /* the record's query and target row in the text */
+    uint64_t origin_start;           /* backbone position of the record's first target base */
+    uint64_t slice_start, slice_end; /* the part's backbone interval */
+    uint64_t out_off;                /* its slot in the pools */
+    uint32_t n_cols;                 /* columns of the record */
+    uint32_t out_cap;
+    uint32_t slot;                   /* its entry of rows[] */
+    uint32_t reserved;
+} pag_cns_slice;
+typedef struct pag_cns_row {
+    uint64_t str_off;     /* = out_off: what pag_cns_aln.str_off takes */
+    uint32_t len;         /* columns */
+    uint32_t n_ins;       /* columns with a query symbol over a target gap */
+    uint32_t n_edge_cols; /* columns whose query is not a gap */
+    uint32_t flag;        /* 0 */
+} pag_cns_row;
+typedef struct pag_cns_rows pag_cns_rows; /* the two device pools of one pag_cns_normalize() */
+int pag_cns_normalize(int device, const char *text, uint64_t text_bytes, const pag_cns_slice *slices, uint64_t n_slices, pag_cns_row *rows,
+                      pag_cns_rows **out);
+/* bytes of each pool; the seconds the call spent uploading and inside its kernels (either pointer may be NULL) */
+uint64_t pag_cns_rows_bytes(const pag_cns_rows *r);
+void pag_cns_rows_times(const pag_cns_rows *r, double *s_upload, double *s_kernels);
+/* in how many pieces the text went up, and how many slices were too long for the kernel's work rows (either may be NULL) */
+void pag_cns_rows_counts(const pag_cns_rows *r, uint64_t *n_pieces, uint64_t *n_oversize);
+/* the pools to host memory (pool_bytes >= pag_cns_rows_bytes) */
+int pag_cns_rows_fetch(const pag_cns_rows *r, char *qpool, char *tpool, uint64_t pool_bytes);
+void pag_cns_rows_free(pag_cns_rows *r);
+/* pag_cns_consensus (wave == 0) or pag_cns_consensus_wave (wave != 0) on rows that are on the device already: nothing of the pools
+ * is uploaded.  Everything else as there. */
+int pag_cns_consensus_rows(int device, int wave, const char *backbone, uint64_t backbone_len, const pag_cns_part *parts, uint64_t n_parts,
+                           const pag_cns_aln *alns, uint64_t n_alns, const pag_cns_rows *rows, int32_t min_weight, char *out, uint64_t out_bytes,
+                           uint64_t *out_off, uint32_t *out_len, int32_t *part_err);
+
 typedef struct pag_kmer_count_result {
     uint64_t min_abundance;
     uint64_t n_solid;
