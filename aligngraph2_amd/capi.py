@@ -25,6 +25,7 @@ CONSTANTS = {
     "PAG_ALN_REV_STRAND": 1, "PAG_ALN_WALK_BACK": 2, "PAG_ALN_ELIGIBLE": 4,
     "PAG_ORIENT_NONE": -1, "PAG_ORIENT_REVERSE": 0, "PAG_ORIENT_FORWARD": 1, "PAG_ORIENT_BOTH": 2,
     "PAG_TRAVEL_RENDER_DUMPS": 1, "PAG_TRAVEL_RENDER_SEQS": 2,
+    "PAG_DEBUG_WALK_GUARD": 16,
 }
 globals().update(CONSTANTS)
 
@@ -45,6 +46,13 @@ DTYPES = {
     "pag_debug_trav_contig": np.dtype([("nodes_off", "<u8"), ("gbits_off", "<u8"), ("gset_off", "<u8"), ("n_kmers", "<u4"),
                                        ("ctg_left", "<u4"), ("ctg_right", "<u4"), ("in_lo", "<u4"), ("in_hi", "<u4"), ("g_lo", "<u4"),
                                        ("g_hi", "<u4"), ("gmask", "<u4")]),
+    # ... the jobs and results of pag_debug_walk
+    "pag_debug_walk_job": np.dtype([("has_size", "<u8"), ("seq_cap", "<u8"), ("init_len", "<u8"), ("set_size", "<u8"), ("out_off", "<u8"),
+                                    ("ctg", "<u4"), ("start", "<u4"), ("exact", "<u4"), ("mode", "<u4"), ("stop_pc", "<u4"), ("win_low", "<u4")]),
+    "pag_debug_walk_out": np.dtype([("seq_len", "<u8"), ("seq_size", "<u8"), ("n_classify", "<u8"), ("n_probe", "<u8"), ("n_records", "<u8"),
+                                    ("n_fill", "<u8"), ("n_out", "<u8"), ("n_main", "<u8"), ("max_probe", "<u8"), ("last_ctg", "<u4"),
+                                    ("overflow", "<u4"), ("stopped", "<u4"), ("max_back", "<u4"), ("max_chosen", "<u4"),
+                                    ("wd_below_max", "<u4"), ("wd_forced_min", "<u4"), ("poison", "<u4")]),
 }
 PAG_DEBUG_NULL = 0xFFFFFFFFFFFFFFFF  # (pagraph_debug.h; as a C long long it is -1, so it is not among CONSTANTS)
 
@@ -175,12 +183,20 @@ class TraverseStats(C.Structure):
 class DebugTravGraph(C.Structure):
     _c_name_ = "pag_debug_trav_graph"
     _fields_ = [("n_nodes", _u64), ("n_pos", _u64), ("k", _u32), ("reserved", _u32), ("ncode", _vp), ("npos_off", _vp), ("vpos", _vp),
-                ("vcnt", _vp), ("vnode", _vp), ("uold", _vp), ("newid", _vp), ("upos", _vp), ("ucnt", _vp), ("bitmap", _vp), ("rank", _vp)]
+                ("vcnt", _vp), ("vnode", _vp), ("uold", _vp), ("newid", _vp), ("upos", _vp), ("ucnt", _vp), ("bitmap", _vp), ("rank", _vp),
+                ("succ_off", _vp), ("succ", _vp), ("incomplete", _vp), ("n_succ", _u64)]
+
+
+class DebugWalkContig(C.Structure):
+    _c_name_ = "pag_debug_walk_contig"
+    _fields_ = [("ctg_left", _u32), ("ctg_right", _u32), ("rev_left", _u32), ("rev_right", _u32), ("split_size", _u64), ("leap_min", _f64),
+                ("n_ctgs", _u32), ("in_lo", _u32), ("in_hi", _u32), ("g_lo", _u32), ("g_hi", _u32), ("gmask", _u32), ("gwin_lo", _u32),
+                ("gwin_hi", _u32), ("starts", _vp), ("sizes", _vp), ("gbits", _vp), ("gset", _vp), ("n_gbits", _u64)]
 
 
 STRUCTS = {s._c_name_: s for s in (PagSeqs, PagAlnDb, PagBuildInput, PagRawDb, PagRawInput, BuildStats, Csr, ShardSlice, Region,
                                    SerialStats, TravelParams, TravelStats, PagSucc, CnsAln, CnsPart, CnsSlice, CnsRow, KmerCountResult, TraverseStats,
-                                   DebugTravGraph)}
+                                   DebugTravGraph, DebugWalkContig)}
 
 # structs of the headers that are deliberately mirrored neither in STRUCTS nor in DTYPES: C name -> why.  (The opaque
 # handles pag_graph and pag_comm have no body to mirror.)
@@ -297,6 +313,8 @@ SIGNATURES = {
     "pag_debug_clear_ranges": (_int, [_vp, _u64, _vp, _u64, _int]),
     "pag_debug_concat_parts": (_int, [_vp, _vp, _u64, _vp, _u32, _vp, _vp, _u64, _u32, _int]),
     "pag_debug_gathers": (_int, [_vp, _int, _vp, _vp, _u64, _u32, _vp, _int]),
+    "pag_debug_walk": (_int, [_vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _u64, _vp, _int]),
+    "pag_debug_walk_geometry": (_int, [_vp, _u32]),
     "pagh_debug_classify_columns": (None, [_cs, _u64, _cs, _u64, _vp, _vp, _vp, _int]),
     "pagh_debug_pack_bases": (None, [_cs, _u64, _vp, _int]),
 }

@@ -574,6 +574,9 @@ __device__ __forceinline__ int walk_straight(WalkLds &L, WalkCtx &X, uint32_t v0
     uint32_t c = (uint32_t)(X.G.upos[v0] >> 32);
     X.max_probe = now_size > X.max_probe ? now_size : X.max_probe;
     if (c != 0 && (c < X.C.ctg_left || c >= X.C.ctg_right)) {
+        // (the probe has visited the coordinate it starts on, like the one a later step leaps to and like the lockstep and single
+        // probes' first vertex: the caller's max_back counts it — nothing is classified against this table any more)
+        win_add(X.win_p0, X.win_p1, c);
         *out_len = len;
         return WS_LEAP;
     }
@@ -1937,3 +1940,196 @@ void trav_launch_walk_persistent(TravGraph G, const TravPosted *jobs, TravJobOut
 }
 
 }  // namespace pagdev
+
+// =================================================================================================
+// test hooks (include/pagraph_debug.h): walk jobs on a graph described by host arrays
+// =================================================================================================
+#include "trav_hook.hpp"
+
+extern "C" int pag_debug_walk_geometry(uint32_t *out, uint32_t n) {
+    using namespace pagdev;
+    if (!out || n != 9u) return PAG_EINVAL;
+    const uint32_t v[9] = {(uint32_t)LIST_CAP, (uint32_t)BR_CAP, (uint32_t)PB_CAP, (uint32_t)PROBE_GROUPS, WIN_IDS, WIN_REC, WIN_BACK, WIN_AHEAD, FILT_WORDS};
+    for (int i = 0; i < 9; ++i) out[i] = v[i];
+    return PAG_OK;
+}
+
+namespace pagdev {
+// one internal buffer of a hook job: `bytes` bytes of `fill`, guard bytes behind them
+constexpr size_t HOOK_GUARD_BYTES = 64;
+constexpr int HOOK_GUARD_FILL = 0x5A;
+static int hook_guarded(HookDev &D, size_t bytes, int fill, void **out, std::vector<void *> &guards) {
+    void *p = nullptr;
+    PAG_HIP_TRY(hipMalloc(&p, bytes + HOOK_GUARD_BYTES));
+    D.bufs.push_back(p);
+    if (bytes) PAG_HIP_TRY(hipMemsetAsync(p, fill, bytes, D.s));
+    PAG_HIP_TRY(hipMemsetAsync((char *)p + bytes, HOOK_GUARD_FILL, HOOK_GUARD_BYTES, D.s));
+    guards.push_back((char *)p + bytes);
+    *out = p;
+    return PAG_OK;
+}
+}  // namespace pagdev
+
+extern "C" int pag_debug_walk(const pag_debug_trav_graph *g, const pag_debug_walk_contig *ctgs, uint32_t n_ctgs, const pag_debug_walk_job *jobs,
+                              uint32_t n_jobs, uint32_t *seq_v, uint32_t *seq_s, uint64_t *seq_x, uint64_t n_seq, pag_debug_walk_out *outs, int device) {
+    using namespace pagdev;
+    if (!g || !ctgs || !n_ctgs || !jobs || !n_jobs || !seq_v || !seq_s || !seq_x || !outs) return PAG_EINVAL;
+    if (!g->newid || !g->upos || !g->ucnt || !g->succ_off || (g->n_succ && !g->succ) || g->n_pos == 0 || g->n_pos >= 0xFFFFFFF0ull || g->n_succ >= 0xFFFFFFF0ull)
+        return PAG_EINVAL;
+    const uint64_t np = g->n_pos;
+    const SuccRec *recs = (const SuccRec *)g->succ;
+    // ---- the graph: every index a walk follows stays inside it
+    if (g->succ_off[0] != 0u || g->succ_off[np] != g->n_succ) return PAG_EINVAL;
+    for (uint64_t u = 0; u < np; ++u)
+        if (g->succ_off[u] > g->succ_off[u + 1] || g->newid[u] >= np) return PAG_EINVAL;
+    for (uint64_t r = 0; r < g->n_succ; ++r) {
+        const SuccRec &R = recs[r];
+        if (R.tgt >= np) return PAG_EINVAL;
+        const uint32_t cnt = g->succ_off[R.tgt + 1] - g->succ_off[R.tgt];
+        const bool marker = ((R.meta >> 24) & 7u) >= GRADE_POISON_IF_LEAP;  // (k_succ_finish writes a marker without a coordinate)
+        if (R.pc != (marker ? 0u : (uint32_t)(g->upos[R.tgt] >> 32)) || R.toff != g->succ_off[R.tgt] || (R.meta >> 28) != (cnt < 15u ? cnt : 15u)) return PAG_EINVAL;
+    }
+    // ---- the contigs
+    for (uint32_t c = 0; c < n_ctgs; ++c) {
+        const pag_debug_walk_contig &C = ctgs[c];
+        if (!(C.g_lo <= C.in_lo && C.in_lo <= C.in_hi && C.in_hi <= C.g_hi && C.g_hi <= np) || ((C.in_lo - C.g_lo) & 31u)) return PAG_EINVAL;
+        if (!C.starts || (C.n_ctgs && !C.sizes) || C.n_ctgs >= 0x7FFFFFFFu) return PAG_EINVAL;
+        for (uint32_t i = 0; i < C.n_ctgs; ++i)
+            if (C.starts[i] > C.starts[i + 1]) return PAG_EINVAL;
+        if ((C.gbits == nullptr) != (C.gset == nullptr)) return PAG_EINVAL;
+        if (C.gbits) {
+            if (C.n_gbits < ((uint64_t)(C.g_hi - C.g_lo) + 31) / 32) return PAG_EINVAL;
+            const uint64_t cap = (uint64_t)C.gmask + 1;
+            if (cap & (cap - 1)) return PAG_EINVAL;
+            bool empty = false;
+            for (uint64_t i = 0; i < cap && !empty; ++i) empty = C.gset[i] == HS_EMPTY;
+            if (!empty) return PAG_EINVAL;
+        }
+    }
+    // ---- the jobs and their ranges of the returned buffers
+    {
+        std::vector<std::pair<uint64_t, uint64_t>> rg;
+        for (uint32_t j = 0; j < n_jobs; ++j) {
+            const pag_debug_walk_job &J = jobs[j];
+            if (J.ctg >= n_ctgs || J.start >= np || J.seq_cap == 0 || J.seq_cap > 0x0FFFFFFFull) return PAG_EINVAL;
+            if (J.set_size < 8 || J.set_size > 0x10000000ull || (J.set_size & (J.set_size - 1))) return PAG_EINVAL;
+            if (J.out_off > n_seq || J.seq_cap + PAG_DEBUG_WALK_GUARD > n_seq - J.out_off) return PAG_EINVAL;
+            rg.emplace_back(J.out_off, J.out_off + J.seq_cap + PAG_DEBUG_WALK_GUARD);
+            const pag_debug_walk_contig &C = ctgs[J.ctg];
+            if (J.mode & TRAV_MODE_RESUME) {
+                if (J.init_len == 0 || J.init_len > J.seq_cap) return PAG_EINVAL;
+                uint64_t outside = 0;
+                for (uint64_t i = 0; i < J.init_len; ++i) {
+                    const uint32_t v = seq_v[J.out_off + i];
+                    if (v >= np) return PAG_EINVAL;
+                    outside += (v < C.in_lo || v >= C.in_hi) ? 1u : 0u;
+                }
+                if (outside > J.set_size - 1) return PAG_EINVAL;
+            } else if (J.init_len != 0) {
+                return PAG_EINVAL;
+            }
+            if (J.mode & ~(uint32_t)(TRAV_MODE_SPEC | TRAV_MODE_RESUME | TRAV_MODE_LEAP | TRAV_MODE_UNTIL_LEAP)) return PAG_EINVAL;
+        }
+        std::sort(rg.begin(), rg.end());
+        for (size_t i = 1; i < rg.size(); ++i)
+            if (rg[i].first < rg[i - 1].second) return PAG_EINVAL;
+    }
+    HookDev D;
+    TravGraph G;
+    int rc;
+    if ((rc = D.open(device)) || (rc = hook_upload_graph(D, g, &G))) return rc;
+    // ---- contig records
+    std::vector<TravContig> hc(n_ctgs);
+    for (uint32_t c = 0; c < n_ctgs; ++c) {
+        const pag_debug_walk_contig &C = ctgs[c];
+        TravContig T{};
+        T.ctg_left = C.ctg_left, T.ctg_right = C.ctg_right, T.rev_left = C.rev_left, T.rev_right = C.rev_right;
+        T.split_size = C.split_size, T.leap_min = C.leap_min, T.n_ctgs = C.n_ctgs;
+        T.in_lo = C.in_lo, T.in_hi = C.in_hi, T.g_lo = C.g_lo, T.g_hi = C.g_hi, T.gmask = C.gmask, T.gwin_lo = C.gwin_lo, T.gwin_hi = C.gwin_hi;
+        uint64_t *d_st = nullptr, *d_sz = nullptr;
+        if ((rc = D.up(C.starts, (uint64_t)C.n_ctgs + 1, &d_st)) || (rc = D.up(C.sizes, (uint64_t)C.n_ctgs, &d_sz))) return rc;
+        T.starts = d_st, T.sizes = d_sz;
+        if (C.gbits) {
+            uint32_t *d_b = nullptr, *d_g = nullptr;
+            if ((rc = D.up(C.gbits, C.n_gbits, &d_b)) || (rc = D.up(C.gset, (uint64_t)C.gmask + 1, &d_g))) return rc;
+            T.gbits = d_b, T.gset = d_g;
+        }
+        hc[c] = T;
+    }
+    TravContig *d_ctgs = nullptr;
+    if ((rc = D.up((const TravContig *)hc.data(), (uint64_t)n_ctgs, &d_ctgs))) return rc;
+    // ---- returned buffers: as the caller filled them, guards included
+    uint32_t *d_sv = nullptr, *d_ss = nullptr;
+    uint64_t *d_sx = nullptr;
+    if ((rc = D.up((const uint32_t *)seq_v, n_seq, &d_sv)) || (rc = D.up((const uint32_t *)seq_s, n_seq, &d_ss)) || (rc = D.up((const uint64_t *)seq_x, n_seq, &d_sx))) return rc;
+    // ---- the jobs' own buffers, as post_batch builds them
+    const uint64_t PG = TRAV_PROBE_GROUPS;
+    std::vector<TravJob> hj(n_jobs);
+    std::vector<void *> guards;
+    for (uint32_t j = 0; j < n_jobs; ++j) {
+        const pag_debug_walk_job &S = jobs[j];
+        const pag_debug_walk_contig &C = ctgs[S.ctg];
+        const uint64_t span = ((uint64_t)(C.in_hi - C.in_lo) + 1 + 3) & ~3ull, cap = S.seq_cap, oc = S.set_size;
+        TravJob J{};
+        void *p_av, *p_as, *p_st, *p_tb, *p_ts, *p_ps;
+        if ((rc = hook_guarded(D, cap * PG * 4, 0, &p_av, guards)) || (rc = hook_guarded(D, cap * PG * 4, 0, &p_as, guards)) ||
+            (rc = hook_guarded(D, PG * span * 4, 0, &p_st, guards)) || (rc = hook_guarded(D, (span + 4) * 4, 0, &p_tb, guards)) ||
+            (rc = hook_guarded(D, oc * 8, 0xFF, &p_ts, guards)) || (rc = hook_guarded(D, oc * PG * 8, 0, &p_ps, guards)))
+            return rc;
+        J.ctg = S.ctg;
+        J.start = S.start;
+        J.has_size = S.has_size;
+        J.seq_v = d_sv + S.out_off;
+        J.seq_s = d_ss + S.out_off;
+        J.seq_cap = cap;
+        J.arena_v = (uint32_t *)p_av;
+        J.arena_s = (uint32_t *)p_as;
+        J.arena_cap = PG * cap;
+        J.stamp = (uint32_t *)p_st;
+        J.stamp_stride = (uint32_t)span;
+        J.tbits = (uint32_t *)p_tb;
+        J.tset = (uint64_t *)p_ts;
+        J.tmask = (uint32_t)oc - 1;
+        J.pset = (uint64_t *)p_ps;
+        J.pmask = (uint32_t)oc - 1;
+        J.exact = S.exact ? 1u : 0u;
+        J.mode = S.mode;
+        J.stop_pc = S.stop_pc;
+        J.init_len = S.init_len;
+        J.win_low = S.win_low;
+        J.seq_x = nullptr;
+        if (S.mode & TRAV_MODE_LEAP) {
+            J.seq_x = d_sx + S.out_off;
+            PAG_HIP_TRY(hipMemsetAsync(J.seq_x, 0, cap * 8, D.s));
+        }
+        hj[j] = J;
+    }
+    TravJob *d_jobs = nullptr;
+    TravJobOut *d_outs = nullptr;
+    if ((rc = D.up((const TravJob *)hj.data(), (uint64_t)n_jobs, &d_jobs)) || (rc = D.up((const TravJobOut *)nullptr, (uint64_t)n_jobs, &d_outs))) return rc;
+    PAG_HIP_TRY(hipMemsetAsync(d_outs, 0, n_jobs * sizeof(TravJobOut), D.s));
+    trav_launch_walk(G, d_ctgs, d_jobs, d_outs, n_jobs, g->k, D.s);
+    std::vector<TravJobOut> ho(n_jobs);
+    std::vector<unsigned char> hg(guards.size() * HOOK_GUARD_BYTES);
+    if ((rc = D.down(ho.data(), (const TravJobOut *)d_outs, (uint64_t)n_jobs)) || (rc = D.down(seq_v, (const uint32_t *)d_sv, n_seq)) ||
+        (rc = D.down(seq_s, (const uint32_t *)d_ss, n_seq)) || (rc = D.down(seq_x, (const uint64_t *)d_sx, n_seq)))
+        return rc;
+    for (size_t q = 0; q < guards.size(); ++q)
+        PAG_HIP_TRY(hipMemcpyAsync(hg.data() + q * HOOK_GUARD_BYTES, guards[q], HOOK_GUARD_BYTES, hipMemcpyDeviceToHost, D.s));
+    if ((rc = D.finish())) return rc;
+    for (uint32_t j = 0; j < n_jobs; ++j) {
+        const TravJobOut &o = ho[j];
+        pag_debug_walk_out w{};
+        w.seq_len = o.seq_len, w.seq_size = o.seq_size, w.n_classify = o.n_classify, w.n_probe = o.n_probe, w.n_records = o.n_records;
+        w.n_fill = o.n_fill, w.n_out = o.n_out, w.n_main = o.n_main, w.max_probe = o.max_probe;
+        w.last_ctg = o.last_ctg, w.overflow = (uint32_t)o.overflow, w.stopped = o.stopped, w.max_back = o.max_back, w.max_chosen = o.max_chosen;
+        w.wd_below_max = o.wd_below_max, w.wd_forced_min = o.wd_forced_min, w.poison = o.poison;
+        outs[j] = w;
+    }
+    for (size_t q = 0; q < hg.size(); ++q)
+        if (hg[q] != (unsigned char)HOOK_GUARD_FILL) {
+            set_error("pag_debug_walk: the guard behind buffer %zu of job %zu was written", (q / HOOK_GUARD_BYTES) % 6, q / HOOK_GUARD_BYTES / 6);
+            return PAG_EFAULT;
+        }
+    return PAG_OK;
+}

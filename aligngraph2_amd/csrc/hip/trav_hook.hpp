@@ -1,5 +1,5 @@
-// What the test hooks on constructed graphs share (include/pagraph_debug.h; defined at the foot of k5_walk_aux.hip and
-// k5_view.hip): the device buffers of one hook call, and the upload of a pag_debug_trav_graph into a TravGraph.  Nothing in the
+// What the test hooks on constructed graphs share (include/pagraph_debug.h; defined at the foot of k5_walk_aux.hip,
+// k5_view.hip and k5_travel.hip): the device buffers of one hook call, and the upload of a pag_debug_trav_graph into a TravGraph.  Nothing in the
 // product includes this.
 #pragma once
 #include <vector>
@@ -79,6 +79,19 @@ inline int hook_upload_graph(HookDev &D, const pag_debug_trav_graph *g, TravGrap
     const uint64_t n_words = ((1ull << (2 * g->k)) + 63) / 64;
     if (g->bitmap && (rc = D.up(g->bitmap, n_words, &G->bitmap))) return rc;
     if (g->rank && (rc = D.up(g->rank, n_words, &G->rank))) return rc;
+    // the walker's arrays (pag_debug_walk checks the records against the graph before it comes here)
+    if (g->succ_off && (rc = D.up(g->succ_off, np + 1, &G->succ_off))) return rc;
+    if (g->succ && g->n_succ) {
+        SuccRec *d = nullptr;
+        if ((rc = D.up((const SuccRec *)g->succ, g->n_succ, &d))) return rc;
+        G->succ = d;
+        G->n_succ = g->n_succ;
+    }
+    if (g->incomplete) {
+        uint32_t *d = nullptr;
+        if ((rc = D.up(g->incomplete, (np + 31) / 32, &d))) return rc;
+        G->incomplete = d;
+    }
     return PAG_OK;
 }
 

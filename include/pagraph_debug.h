@@ -86,6 +86,12 @@ typedef struct pag_debug_trav_graph {
     const uint32_t *ucnt;     /* [n_pos] abundances by new id */
     const uint64_t *bitmap;   /* [(4^k + 63) / 64] */
     const uint32_t *rank;     /* [(4^k + 63) / 64] */
+    /* what the walker waves read beside newid / upos / ucnt (pag_debug_walk) */
+    const uint32_t *succ_off; /* [n_pos + 1] successor records of new id u; succ_off[n_pos] = n_succ */
+    const void *succ;         /* [n_succ] records of 16 bytes: tgt, pc, meta, toff (SuccRec, pag_travel.hpp) */
+    const uint32_t *incomplete; /* [(n_pos + 31) / 32] bit u: the records of u are a marker (may be NULL).  Uploaded into
+                                 * TravGraph::incomplete and nothing more: a walk reads the marker RECORDS, never this bitmap */
+    uint64_t n_succ;
 } pag_debug_trav_graph;
 /* the fields of a TravContig (pag_travel.hpp) these kernels read, by value; its three pointers as word offsets into the arrays
  * `nodes`, `gbits`, `gset` given beside the records (PAG_DEBUG_NULL: a null pointer) */
@@ -125,6 +131,62 @@ int pag_debug_concat_parts(const uint32_t *src_v, const uint32_t *src_s, uint64_
  * k_gather_vertices over the k-mer-major ids seq_v (out: pag_path_node[len]; seq_s, max_blocks not read) */
 int pag_debug_gathers(const pag_debug_trav_graph *g, int which, const uint32_t *seq_v, const uint32_t *seq_s, uint64_t len, uint32_t max_blocks,
                       void *out, int device);
+
+/* The walker wave itself (walk_job of k5_travel.hip: graphTravel / walkStraight / classifySuccessors over the successor records) on
+ * a CONSTRUCTED graph (tests/test_gpu_walk.py against tests/walk_rule.py).  The graph is g's newid / upos / ucnt / succ_off / succ
+ * (all required).  ctgs[n_ctgs]: the TravContig records by value, their arrays as host pointers (starts[n_ctgs + 1], sizes[n_ctgs];
+ * gbits[n_gbits] a bitmap over [g_lo, g_hi), gset[gmask + 1], both NULL or both given).  jobs[n_jobs]: one walk each.
+ *
+ * Buffers.  seq_v / seq_s / seq_x[n_seq] are uploaded as the caller filled them and come back whole.  Job j owns the entries
+ * [out_off, out_off + seq_cap) of each, followed by PAG_DEBUG_WALK_GUARD guard entries inside the same allocation which no job may
+ * touch (the caller fills them and compares them afterwards); the ranges of the jobs, guards included, must not overlap.  A
+ * RESUME job finds the init_len entries of its path at the head of its seq_v / seq_s range.  seq_x is handed to a LEAP job only,
+ * its range zeroed first.  The other buffers of a job are built as post_batch (walk_session_jobs.hpp) builds them, each in an
+ * allocation of its own with guard words behind it that the hook itself checks (PAG_EFAULT when one was written):
+ *   stamp  TRAV_PROBE_GROUPS arrays of `stride` words, stride = (in_hi - in_lo + 1) rounded up to a multiple of four; zeroed
+ *   tbits  stride + 4 words, zeroed
+ *   tset   set_size 64-bit entries, all ones;  pset  TRAV_PROBE_GROUPS x set_size entries, zeroed (tmask = pmask = set_size - 1)
+ *   arena  TRAV_PROBE_GROUPS x seq_cap entries for vertices and as many for steps
+ * The launch is trav_launch_walk — the one-shot k_walk, the same walk_job body as the persistent grid; the persistent kernel and
+ * its queue are never started here.  outs[n_jobs] is TravJobOut in plain C (n_fill: bits 32.. hold the reasons of a
+ * mis-speculation, as the kernel reports them).
+ *
+ * Refused with PAG_EINVAL before anything is launched — what would let the kernel read or write outside these buffers: a record
+ * with tgt >= n_pos, or whose pc / toff / count nibble disagree with upos[tgt] >> 32 (a marker record, grade 6 or 7: 0), succ_off[tgt] and min(count of tgt, 15);
+ * succ_off not starting at 0, not monotonic or not ending at n_succ; newid[start] (or start) out of range; a contig without
+ * g_lo <= in_lo <= in_hi <= g_hi <= n_pos, with in_lo - g_lo no multiple of 32, a bitmap shorter than its range, starts not
+ * ascending, a gset that is no power of two in size or has no empty entry; seq_cap = 0; a RESUME path that is empty, longer
+ * than seq_cap, names a vertex >= n_pos or has more vertices outside [in_lo, in_hi) than set_size - 1; a set_size that is no
+ * power of two or below 8; overlapping output ranges.
+ * Termination needs no guard of its own: every vertex a walk or a probe appends is marked first and a marked vertex is never
+ * accepted again, every append to the sequence is bounded by seq_cap and every probe by its share of the arena (both end the
+ * job with overflow set), and a hash set is never searched without an empty entry — the load-factor tests end the job before
+ * (n_out * 2 > tmask, (po.n + 1) * 2 > pmask, with tmask = pmask), which the limit on a RESUME path extends to its take-over. */
+#define PAG_DEBUG_WALK_GUARD 16
+typedef struct pag_debug_walk_contig {
+    uint32_t ctg_left, ctg_right, rev_left, rev_right;
+    uint64_t split_size;
+    double leap_min;
+    uint32_t n_ctgs, in_lo, in_hi, g_lo, g_hi, gmask, gwin_lo, gwin_hi;
+    const uint64_t *starts; /* [n_ctgs + 1] */
+    const uint64_t *sizes;  /* [n_ctgs] */
+    const uint32_t *gbits;  /* [n_gbits] or NULL */
+    const uint32_t *gset;   /* [gmask + 1] or NULL */
+    uint64_t n_gbits;
+} pag_debug_walk_contig;
+typedef struct pag_debug_walk_job {
+    uint64_t has_size, seq_cap, init_len, set_size, out_off;
+    uint32_t ctg, start, exact, mode, stop_pc, win_low;
+} pag_debug_walk_job;
+typedef struct pag_debug_walk_out {
+    uint64_t seq_len, seq_size, n_classify, n_probe, n_records, n_fill, n_out, n_main, max_probe;
+    uint32_t last_ctg, overflow, stopped, max_back, max_chosen, wd_below_max, wd_forced_min, poison;
+} pag_debug_walk_out;
+int pag_debug_walk(const pag_debug_trav_graph *g, const pag_debug_walk_contig *ctgs, uint32_t n_ctgs, const pag_debug_walk_job *jobs,
+                   uint32_t n_jobs, uint32_t *seq_v, uint32_t *seq_s, uint64_t *seq_x, uint64_t n_seq, pag_debug_walk_out *outs, int device);
+/* the walker's geometry as built (make WALK_WINDOW=...): out[9] = LIST_CAP, BR_CAP, PB_CAP, PROBE_GROUPS, WIN_IDS, WIN_REC, WIN_BACK,
+ * WIN_AHEAD, FILT_WORDS.  No device is touched. */
+int pag_debug_walk_geometry(uint32_t *out, uint32_t n);
 
 /* ---- libpagraph_host.so ---- */
 /* one record's column classes / one sequence packed, by the production path or by the scalar loop alone */
