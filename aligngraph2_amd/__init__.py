@@ -65,6 +65,40 @@ def load_host():
     return _host["lib"]
 
 
+def successors_batch(hip, g, codes, pos, deviation, error_rate):
+    """pag_successors_batch (include/pagraph_hip.h) for the vertices (codes[i], pos[i]) of the finished graph in handle `g` of
+    the bound library `hip`: a sizing call, then the real one.  Returns (off, status, records): off[n + 1] uint64, status[n]
+    int32 (capi.PAG_OK, or capi.PAG_EINVAL where the graph holds no such vertex: an empty list), records off[-1] entries of
+    capi.PagSucc as a numpy record array (code, step, pos, grade, ctg_similar), list i at records[off[i]:off[i + 1]]."""
+    import numpy as np
+
+    codes = np.asarray(codes)
+    pos = np.asarray(pos)
+    if codes.shape != pos.shape or codes.ndim != 1:
+        raise ValueError("codes and pos are one-dimensional arrays of the same length")
+    n = len(codes)
+    q = np.zeros(n, dtype=np.dtype(capi.PagSuccQuery))
+    q["code"], q["pos"] = codes, pos
+    off = np.zeros(n + 1, dtype=np.uint64)
+    status = np.zeros(n, dtype=np.int32)
+    total = C.c_uint64()
+    handle = g if isinstance(g, C.c_void_p) else C.c_void_p(g)
+
+    def call(out, cap):
+        return hip.pag_successors_batch(handle, q.ctypes.data, n, int(deviation), float(error_rate), off.ctypes.data, status.ctypes.data,
+                                        out, cap, C.byref(total), None)
+
+    rc = call(None, 0)
+    if rc not in (capi.PAG_OK, capi.PAG_ERANGE) or (rc == capi.PAG_ERANGE and total.value == 0):
+        raise RuntimeError(f"pag_successors_batch failed ({rc}): {hip.pag_last_error().decode()}")
+    records = np.zeros(total.value, dtype=np.dtype(capi.PagSucc))
+    if total.value:
+        rc = call(records.ctypes.data, len(records))
+        if rc != capi.PAG_OK:
+            raise RuntimeError(f"pag_successors_batch failed ({rc}): {hip.pag_last_error().decode()}")
+    return off, status, records
+
+
 def pagraph_argv(binary, in_dir, out_dir, threads=1, epsilon=10, cov=2, min_len=50):
     """The argv AlignGraph2.py uses for pagraph (reference AlignGraph2.py:414-427), incl. the doubled -r."""
     return [binary, "-t", str(threads), "-r", "dummy", "-k", os.path.join(in_dir, "kmer.bin"),

@@ -145,6 +145,11 @@ class PagSucc(C.Structure):
     _fields_ = [("code", _u32), ("step", _u32), ("pos", _u64), ("grade", _u32), ("ctg_similar", _u32)]
 
 
+class PagSuccQuery(C.Structure):
+    _c_name_ = "pag_succ_query"
+    _fields_ = [("code", _u32), ("reserved", _u32), ("pos", _u64)]
+
+
 class CnsAln(C.Structure):
     _c_name_ = "pag_cns_aln"
     _fields_ = [("str_off", _u64), ("len", _u32), ("start", _u32), ("weight", _i32), ("reserved", _u32)]
@@ -195,7 +200,7 @@ class DebugWalkContig(C.Structure):
 
 
 STRUCTS = {s._c_name_: s for s in (PagSeqs, PagAlnDb, PagBuildInput, PagRawDb, PagRawInput, BuildStats, Csr, ShardSlice, Region,
-                                   SerialStats, TravelParams, TravelStats, PagSucc, CnsAln, CnsPart, CnsSlice, CnsRow, KmerCountResult, TraverseStats,
+                                   SerialStats, TravelParams, TravelStats, PagSucc, PagSuccQuery, CnsAln, CnsPart, CnsSlice, CnsRow, KmerCountResult, TraverseStats,
                                    DebugTravGraph, DebugWalkContig)}
 
 # structs of the headers that are deliberately mirrored neither in STRUCTS nor in DTYPES: C name -> why.  (The opaque
@@ -251,6 +256,8 @@ SIGNATURES = {
     "pag_travel_view_sizes": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pag_travel": (_int, [_vp, _vp, _vp, _vp, _u64, _vp, _vp]),
     "pag_successors": (_i64, [_vp, _u32, _u64, _vp, _u64]),
+    "pag_successors_batch": (_int, [_vp, _vp, _u64, _u64, _f64, _vp, _vp, _vp, _u64, _u64p, _vp]),
+    "pag_successors_batch_bytes": (_u64, [_u64, _u64]),
     "pag_travel_path": (_vp, [_vp, _u64, _u64p]),
     "pag_travel_path_oriented": (_vp, [_vp, _u64, _int, _u64p]),
     "pag_reserve_walk_arena": (_int, [_vp, _u64]),

@@ -437,6 +437,30 @@ typedef struct pag_succ {
     uint32_t ctg_similar; /* isEdgeSimilar().first */
 } pag_succ;
 int64_t pag_successors(const pag_graph *g, uint32_t code, uint64_t pos, pag_succ *out, uint64_t cap);
+/* The same question asked of the FINISHED GRAPH, for a list of vertices and with the caller's own deviation and error rate:
+ * the lists are evaluated on demand (csrc/hip/k_succ_query.hip, one wavefront per query) from the arrays pag_process /
+ * pag_shard_import leave in the handle.  No view is needed, built or changed: the call works before, after and without
+ * pag_travel_prepare*, and pag_travel, pag_successors and pag_export_csr see the handle as they would without it.  The walker's
+ * marks play no part: this is the reference's call on a fresh graph.
+ * All pointers are HOST memory.  q[i] names a vertex as pag_successors does; the lists come in query order, a vertex named
+ * twice gets its list twice: out[off[i] .. off[i + 1]) is the list of q[i], in the reference's order (edge order, then position
+ * order), grade and ctg_similar as in pag_succ.  A q[i] that names no vertex (a k-mer the graph lacks, a k-mer without that
+ * position) has an empty list and status[i] = PAG_EINVAL (status may be NULL; PAG_OK otherwise) and does not fail the call.
+ * *n_total always receives the number of records of all lists and off[0 .. n_q] is complete whenever the lists were counted;
+ * PAG_ERANGE when *n_total > cap (nothing is written to out then; out may be NULL when cap is 0: a sizing call).  n_q = 0:
+ * PAG_OK, off[0] = 0.  PAG_EINVAL when the handle holds no finished graph; PAG_ERANGE when it holds one rank's region of a block
+ * (pag_shard_set_region): a region does not hold every successor of its vertices.
+ * *ms_kernels (may be NULL): device time of the call's kernels from events — the lists are counted, the counts scanned, the
+ * lists filled; copies and allocations are not in it.  The call's temporary device memory is a plain allocation of its own,
+ * freed before it returns (no pool slot): pag_successors_batch_bytes(n_q, n_records) bytes for n_records records written. */
+typedef struct pag_succ_query {
+    uint32_t code;     /* k-mer */
+    uint32_t reserved; /* 0 */
+    uint64_t pos;      /* contig coordinate << 32 | reference coordinate */
+} pag_succ_query;
+int pag_successors_batch(const pag_graph *g, const pag_succ_query *q, uint64_t n_q, uint64_t deviation, double error_rate,
+                         uint64_t *off, int32_t *status, pag_succ *out, uint64_t cap, uint64_t *n_total, double *ms_kernels);
+uint64_t pag_successors_batch_bytes(uint64_t n_q, uint64_t n_records);
 const pag_path_node *pag_travel_path(const pag_graph *g, uint64_t ctg_index, uint64_t *len);
 const pag_path_node *pag_travel_path_oriented(const pag_graph *g, uint64_t ctg_index, int forward, uint64_t *len);
 /* Optional: have the device memory the walks of pag_travel take their job buffers from (one arena per handle, kept between
