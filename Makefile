@@ -165,6 +165,12 @@ tests/harness/bin/cns_rows_sanitized: tests/harness/cns_rows_main.cpp $(HIP_DIR)
 	@mkdir -p tests/harness/bin
 	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=all -I$(HIP_DIR) -o $@ $<
 
+# bin/pa_cns itself (its host code: the ingests, the flat backend, the batch engine) as a program of its own under the address and
+# undefined-behaviour sanitizers (built and run by tests/test_pa_cns_batch.py on a manifest of jobs, flat backend)
+tests/harness/bin/pa_cns_sanitized: $(HOST_DIR)/pa_cns_main.cpp $(HOST_DIR)/seq_db.cpp $(wildcard $(HOST_DIR)/*.hpp) $(HIP_DIR)/cns_graph.hpp $(HIP_DIR)/cns_rows.hpp include/pagraph_hip.h
+	@mkdir -p tests/harness/bin
+	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude -I$(HOST_DIR) -o $@ $(HOST_DIR)/pa_cns_main.cpp $(HOST_DIR)/seq_db.cpp -ldl -pthread
+
 clean:
 	rm -rf $(B) aligngraph2_amd/libpagraph_hip.so aligngraph2_amd/bin tests/harness/bin
 	$(MAKE) -C oracle clean

@@ -9,6 +9,7 @@ There is no CPU fallback: without the HIP library (or without a gfx950 device) e
 import ctypes as C
 import os
 import subprocess
+import tempfile
 
 from . import capi
 
@@ -17,6 +18,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(PKG, "libpagraph_hip.so")
 HOST_LIB = os.path.join(PKG, "libpagraph_host.so")
 PAGRAPH = os.path.join(PKG, "bin", "pagraph")
+PA_CNS = os.path.join(PKG, "bin", "pa_cns")
 
 
 def build(targets=("product",)):
@@ -34,6 +36,23 @@ def run_pagraph(argv, **kw):
     """Run the drop-in executable with the reference's argv (AlignGraph2.py:414-427) minus argv[0]."""
     require_built()
     return subprocess.run([PAGRAPH, *argv], **kw)
+
+
+def run_pa_cns_batch(jobs, part_len=5000, top_k=3000, alpha=250, threads=16, **kw):
+    """The consensus step for many contigs in one run (`pa_cns --batch`): jobs is a sequence of (backbone FASTA, 3-line ALN file,
+    output FASTA), the parts of all of them go through the graph stage together.  Every output file and the three stdout lines per
+    job, in the order of jobs, are what one `pa_cns -i -a -o` run per job writes (AlignGraph2.py:500-510).  **kw goes to
+    subprocess.run; returns the CompletedProcess."""
+    if not os.path.exists(PA_CNS):
+        raise RuntimeError(f"{PA_CNS} is missing — run aligngraph2_amd.build()")
+    jobs = [tuple(os.fspath(p) for p in job) for job in jobs]
+    for job in jobs:
+        if len(job) != 3 or any("\t" in p or "\n" in p or not p for p in job):
+            raise ValueError(f"a job is (backbone, alignments, output), three paths without TAB or newline: {job!r}")
+    with tempfile.NamedTemporaryFile("w", suffix=".pa_cns_batch.tsv") as manifest:
+        manifest.write("".join("\t".join(job) + "\n" for job in jobs))
+        manifest.flush()
+        return subprocess.run([PA_CNS, "-t", str(threads), "-l", str(part_len), "-k", str(top_k), "--alpha", str(alpha), "--batch", manifest.name], **kw)
 
 
 _hip = {}

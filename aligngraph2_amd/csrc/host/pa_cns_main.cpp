@@ -19,6 +19,9 @@
 // normalised on the device (pag_cns_normalize, csrc/hip/k_cns_rows.hip) where the graph kernels read them next.  A file with a
 // record that is not regular (ingestParallel below) goes through `host`: that is where the reference's arithmetic wraps.
 //
+// Many backbones in one run: --batch <manifest> (runBatch at the end of this file) gathers the jobs of a manifest into groups and
+// hands a group's parts to the backend in one call; every job's file and stdout lines are the single run's.
+//
 // What has to be reproduced beyond the arithmetic, because it decides ties:
 //   * the graph is boost::adjacency_list<vecS, vecS, bidirectionalS>: out- and in-edge lists are vectors in insertion order,
 //     clear_vertex() erases entries in place (order of the others kept), edge(u, v) finds the first match in u's out list,
@@ -38,9 +41,11 @@
 #include <cstring>
 #include <dlfcn.h>
 #include <fstream>
+#include <future>
 #include <iostream>
 #include <map>
 #include <memory>
+#include <numeric>
 #include <queue>
 #include <sstream>
 #include <string>
@@ -527,6 +532,7 @@ struct Options {
     unsigned threads = 16;
     std::size_t partLen = 5000, topK = 3000, alpha = 250;
     std::string in, out, align;
+    std::string batch;  // --batch: a manifest of jobs (backbone, alignments, output) instead of -i / -a / -o
 };
 void usage(std::ostream &os) {
     os << "  pa_cns {OPTIONS}\n\n  OPTIONS:\n\n"
@@ -537,7 +543,8 @@ void usage(std::ostream &os) {
           "      --alpha=[alpha]                   alpha\n"
           "      -i[path], --in=[path]             input of backbone\n"
           "      -o[path], --out=[path]            output of file\n"
-          "      -a[path], --align=[path]          alignments file\n";
+          "      -a[path], --align=[path]          alignments file\n"
+          "      --batch=[manifest]                many jobs in one run: a line per job, backbone TAB alignments TAB output (instead of -i -a -o)\n";
 }
 struct ParseError : std::runtime_error {
     using std::runtime_error::runtime_error;
@@ -561,10 +568,11 @@ Options parseCli(int argc, char **argv) {
         else if (name == "i" || name == "in") o.in = value;
         else if (name == "o" || name == "out") o.out = value;
         else if (name == "a" || name == "align") o.align = value;
+        else if (name == "batch") o.batch = value;
         else throw ParseError("Flag could not be matched: " + name);
     };
     auto isLong = [](const std::string &n) {
-        for (const char *x : {"thread", "len", "top_k", "alpha", "in", "out", "align"})
+        for (const char *x : {"thread", "len", "top_k", "alpha", "in", "out", "align", "batch"})
             if (n == x) return true;
         return false;
     };
@@ -598,6 +606,8 @@ Options parseCli(int argc, char **argv) {
             throw ParseError("Passed in argument, but no positional arguments were ready to receive it: " + a);
         }
     }
+    if (!o.batch.empty() && !(o.in.empty() && o.out.empty() && o.align.empty()))
+        throw ParseError("Flag 'batch' names the inputs and outputs of every job: it cannot be combined with 'i', 'a' or 'o'");
     return o;
 }
 
@@ -874,6 +884,233 @@ bool ingestParallel(const std::string &path, const std::string &skeleton, std::s
     return true;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The pieces of a run: load the backbone; ingest (ingestParallel above, or readFromRefFile + sortAndCut + flattenParts);
+// size the parts; run the graphs; write the output.  main() runs them for one job, runBatch() for the jobs of a manifest.
+// ---------------------------------------------------------------------------------------------------------------------
+using Clock = std::chrono::steady_clock;
+inline double seconds(Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double>(b - a).count(); }
+
+struct Backbone {
+    std::string name, seq;
+};
+// the first sequence of the file; false when there is none (a file that cannot be opened is an empty database in the reference,
+// AutoSeqDatabase.cpp:9-22)
+bool loadBackbone(const std::string &path, Backbone &bb) {
+    pagh::SeqDb seqDatabase;
+    try {
+        seqDatabase = pagh::SeqDb(path);
+    } catch (const std::exception &) {
+    }
+    if (seqDatabase.size() == 0) return false;
+    bb.name = seqDatabase.name(0);
+    bb.seq = seqDatabase.toString(0, true);
+    return true;
+}
+
+// std::sort by score, descending, and the cut to -k: the same algorithm on a proxy array (the tie order is the library's)
+void sortAndCut(std::vector<ScoredAln> &alns, std::size_t topK) {
+    struct Proxy {
+        unsigned score;
+        std::size_t idx;
+    };
+    std::vector<Proxy> proxy(alns.size());
+    for (std::size_t x = 0; x < alns.size(); ++x) proxy[x] = Proxy{alns[x].score, x};
+    std::sort(proxy.begin(), proxy.end(), [](const Proxy &l, const Proxy &r) { return l.score > r.score; });
+    std::vector<ScoredAln> sorted;
+    sorted.reserve(std::min(alns.size(), topK));
+    for (std::size_t x = 0; x < proxy.size() && x < topK; ++x) sorted.push_back(std::move(alns[proxy[x].idx]));
+    alns.swap(sorted);
+}
+
+// The host ingest's lists as flat arrays: every alignment's two rows in two pools, and per part what sizes its graph.  (The
+// lists are released as they are copied: their rows live in the pools then.)
+struct HostRows {
+    std::vector<pag_cns_aln> flat;
+    std::vector<std::uint64_t> partFirst, nIns, nEdgeCols;
+    std::string qpool, tpool;
+};
+void flattenParts(std::vector<std::vector<ScoredAln>> &alignments, const std::vector<std::vector<std::size_t>> &partWeights, HostRows &out) {
+    const std::size_t partNum = alignments.size();
+    out.partFirst.assign(partNum + 1, 0);
+    out.nIns.assign(partNum, 0);
+    out.nEdgeCols.assign(partNum, 0);
+    for (std::size_t i = 0; i < partNum; ++i) {
+        const auto &alns = alignments[i];
+        for (std::size_t x = 0; x < partWeights[i].size(); ++x) {
+            const Aln &a = alns[x].aln;
+            pag_cns_aln f{};
+            f.str_off = out.qpool.size();
+            f.len = static_cast<std::uint32_t>(a.qstr.size());
+            f.start = a.start;
+            f.weight = static_cast<std::int32_t>(partWeights[i][x]);
+            out.flat.push_back(f);
+            out.qpool += a.qstr;
+            out.tpool += a.tstr;
+            for (std::size_t c = 0; c < a.qstr.size(); ++c) {
+                const char qb = a.qstr[c], tb = a.tstr[c];
+                if (qb != '-' && tb == '-') ++out.nIns[i];
+                if (qb != '-') ++out.nEdgeCols[i];
+            }
+        }
+        std::vector<ScoredAln>().swap(alignments[i]);
+        out.partFirst[i + 1] = out.flat.size();
+    }
+}
+
+// The parts of one backbone: the regions of every part's graph sized from its columns (include/pagraph_hip.h,
+// pag_cns_consensus).  bbBase / alnBase: where the backbone and the alignments of this job start in the arrays the backend
+// gets (0 for a single job).  Appends to `parts`.
+void sizeParts(std::size_t bbLen, std::size_t partLen, const std::vector<std::uint64_t> &partFirst, const std::vector<std::uint64_t> &nIns,
+               const std::vector<std::uint64_t> &nEdgeCols, std::uint64_t bbBase, std::uint64_t alnBase, std::vector<pag_cns_part> &parts) {
+    const std::size_t partNum = (bbLen + partLen - 1) / partLen;
+    for (std::size_t i = 0; i < partNum; ++i) {
+        const std::size_t left = i * partLen, right = std::min((i + 1) * partLen, bbLen);
+        pag_cns_part P{};
+        P.bb_off = bbBase + left;
+        P.bb_len = static_cast<std::uint32_t>(right - left);
+        P.aln_first = alnBase + partFirst[i];
+        P.n_aln = static_cast<std::uint32_t>(partFirst[i + 1] - partFirst[i]);
+        const std::uint64_t nodeCap = P.bb_len + 2ull + nIns[i], edgeCap = P.bb_len + 1ull + nEdgeCols[i] + P.n_aln + 4096ull;
+        if (nodeCap > 0x7FFFFFFFull || edgeCap > 0x7FFFFFFFull) throw std::runtime_error("pa_cns: a part with more than 2^31 graph slots");
+        P.node_cap = static_cast<std::uint32_t>(nodeCap);
+        P.edge_cap = static_cast<std::uint32_t>(edgeCap);
+        P.aux_cap = static_cast<std::uint32_t>(std::min<std::uint64_t>(4 * nodeCap + 2048, 0x7FFFFFFFull));
+        P.out_cap = P.node_cap;
+        parts.push_back(P);
+    }
+}
+
+// What a backend call gets and what it leaves: part p's consensus is buf[off[p] .. + len[p]), err[p] != 0 says why there is none
+struct GraphIo {
+    const char *backbone = nullptr;
+    std::uint64_t backboneLen = 0;
+    const std::vector<pag_cns_part> *parts = nullptr;
+    const std::vector<pag_cns_aln> *flat = nullptr;
+    const char *qrows = nullptr, *trows = nullptr;  // (null: the rows are on the device, in `dev`)
+    std::uint64_t poolBytes = 0;
+    pag_cns_rows *dev = nullptr;
+    std::vector<char> buf;
+    std::uint64_t outBytes = 0;  // the parts' out_cap together (buf holds 16 more)
+    std::vector<std::uint64_t> off;
+    std::vector<std::uint32_t> len;
+    std::vector<std::int32_t> err;
+    void prepare() {
+        outBytes = 0;
+        for (const pag_cns_part &P : *parts) outBytes += P.out_cap;
+        buf.assign(outBytes + 16, 0);
+        off.assign(parts->size() + 1, 0);
+        len.assign(parts->size(), 0);
+        err.assign(parts->size(), 0);
+    }
+};
+
+// the device's code (csrc/hip/cns_graph.hpp) on host threads; phaseNs (with PA_CNS_STAGE_TIMES): add_aln, merge_nodes, best_path + trim
+void runFlatBackend(GraphIo &io, unsigned nThreads, bool stageTimes, std::atomic<long long> *phaseNs) {
+    const std::vector<pag_cns_part> &parts = *io.parts;
+    const std::size_t partNum = parts.size();
+    std::uint64_t oo = 0;
+    for (std::size_t i = 0; i < partNum; ++i) {
+        io.off[i] = oo;
+        oo += parts[i].out_cap;
+    }
+    io.off[partNum] = oo;
+    std::atomic<std::size_t> nextPart(0);
+    auto flatWork = [&]() {
+        for (std::size_t i; (i = nextPart.fetch_add(1)) < partNum;) {
+            const pag_cns_part &S = parts[i];
+            std::vector<std::uint8_t> nb(S.node_cap), nf(S.node_cap), ev(S.edge_cap);
+            std::vector<std::int32_t> ncov(S.node_cap), nw(S.node_cap), nbest(S.node_cap), ec(S.edge_cap);
+            std::vector<std::uint32_t> nu[7], eu[6], aux(S.aux_cap);
+            for (auto &v : nu) v.resize(S.node_cap);
+            for (auto &v : eu) v.resize(S.edge_cap);
+            std::vector<float> nscore(S.node_cap);
+            pagcns::Arrays A{nb.data(), nf.data(), ncov.data(), nw.data(), nu[0].data(), nu[1].data(), nu[2].data(), nu[3].data(), nu[4].data(), nu[5].data(),
+                             nu[6].data(), nscore.data(), nbest.data(), eu[0].data(), eu[1].data(), eu[2].data(), eu[3].data(), eu[4].data(), eu[5].data(),
+                             ec.data(), ev.data(), aux.data()};
+            pagcns::Part P{};
+            P.bb_off = S.bb_off;
+            P.bb_len = S.bb_len;
+            P.n_aln = S.n_aln;
+            P.aln_first = S.aln_first;
+            P.out_off = io.off[i];
+            P.node_cap = S.node_cap;
+            P.edge_cap = S.edge_cap;
+            P.aux_cap = S.aux_cap;
+            P.out_cap = S.out_cap;
+            static_assert(sizeof(pag_cns_aln) == sizeof(pagcns::Aln), "pag_cns_aln is pagcns::Aln");
+            std::uint32_t len = 0;
+            const auto *fa = reinterpret_cast<const pagcns::Aln *>(io.flat->data());
+            if (!stageTimes) {
+                io.err[i] = pagcns::run_part(A, P, io.backbone, fa, io.qrows, io.trows, 0, io.buf.data(), &len);
+            } else {  // run_part's steps with a clock between them
+                pagcns::Graph g;
+                pagcns::bind(g, A, P);
+                const auto t0 = Clock::now();
+                pagcns::init_backbone(g, io.backbone + P.bb_off, P.bb_len);
+                for (std::uint32_t a = 0; a < P.n_aln && !g.err; ++a) {
+                    const pagcns::Aln &al = fa[P.aln_first + a];
+                    pagcns::add_aln(g, io.qrows + al.str_off, io.trows + al.str_off, al.len, al.start, al.weight);
+                }
+                const auto t1 = Clock::now();
+                if (!g.err) pagcns::merge_nodes(g);
+                const auto t2 = Clock::now();
+                if (!g.err) pagcns::consensus(g, 0, io.buf.data() + P.out_off, P.out_cap, &len);
+                const auto t3 = Clock::now();
+                phaseNs[0] += std::chrono::duration_cast<std::chrono::nanoseconds>(t1 - t0).count();
+                phaseNs[1] += std::chrono::duration_cast<std::chrono::nanoseconds>(t2 - t1).count();
+                phaseNs[2] += std::chrono::duration_cast<std::chrono::nanoseconds>(t3 - t2).count();
+                io.err[i] = g.err;
+            }
+            io.len[i] = io.err[i] ? 0 : len;
+        }
+    };
+    std::vector<std::thread> pool;
+    for (unsigned t = 1; t < nThreads; ++t) pool.emplace_back(flatWork);
+    flatWork();
+    for (auto &t : pool) t.join();
+}
+
+// hip: one device thread per part (csrc/hip/k_cns.hip); wave: a wavefront per part (csrc/hip/k_cns_wave.hip).  The call fails
+// without a gfx950 device: there is no silent fallback.
+void runDeviceBackend(HipLibrary &hip, bool wave, int device, GraphIo &io) {
+    const std::uint64_t outBytes = io.outBytes;
+    const int rc = io.dev ? hip.consensus_rows(device, wave ? 1 : 0, io.backbone, io.backboneLen, io.parts->data(), io.parts->size(), io.flat->data(), io.flat->size(),
+                                               io.dev, 0, io.buf.data(), outBytes, io.off.data(), io.len.data(), io.err.data())
+                          : (wave ? hip.consensus_wave : hip.consensus)(device, io.backbone, io.backboneLen, io.parts->data(), io.parts->size(), io.flat->data(),
+                                                                        io.flat->size(), io.qrows, io.trows, io.poolBytes, 0, io.buf.data(), outBytes, io.off.data(),
+                                                                        io.len.data(), io.err.data());
+    if (rc != 0)
+        throw std::runtime_error(std::string(io.dev ? "pag_cns_consensus_rows" : wave ? "pag_cns_consensus_wave" : "pag_cns_consensus") + " failed (" + std::to_string(rc) +
+                                 "): " + hip.last_error());
+}
+
+// what a part's error code says (the failures a run reports besides a library error)
+std::string partFailure(std::size_t part, std::int32_t err) {
+    if (err == pagcns::CNS_E_OVERRUN) return "pa_cns: an alignment runs past the end of its part";
+    return "pa_cns: part " + std::to_string(part) + " ran out of its graph regions (code " + std::to_string(err) + ")";
+}
+
+// one FASTA record, 70 columns, of the parts' consensus strings
+std::string fastaText(const std::string &name, std::size_t backboneLen, const std::vector<std::string> &consensusResults) {
+    std::string text;
+    text.reserve(backboneLen + backboneLen / 70 + name.size() + 8);
+    text += ">" + name + "\n";
+    std::size_t cnt = 0;
+    for (auto &seq : consensusResults)
+        for (char ch : seq) {
+            text += ch;
+            if (++cnt % 70 == 0) {
+                text += '\n';
+                cnt = 0;
+            }
+        }
+    if (cnt > 0) text += '\n';
+    return text;
+}
+
+int runBatch(const Options &opt);
+
 int main(int argc, char **argv) {
     if (argc <= 1) {
         usage(std::cerr);
@@ -890,18 +1127,14 @@ int main(int argc, char **argv) {
         usage(std::cerr);
         return 1;
     }
+    if (!opt.batch.empty()) return runBatch(opt);
     try {
-        pagh::SeqDb seqDatabase;
-        try {
-            seqDatabase = pagh::SeqDb(opt.in);
-        } catch (const std::exception &) {  // (a file that cannot be opened is an empty database in the reference, AutoSeqDatabase.cpp:9-22)
-        }
-        if (seqDatabase.size() == 0) {
+        Backbone bb;
+        if (!loadBackbone(opt.in, bb)) {
             std::cerr << "[Error] No backbone" << std::endl;
             return 2;
         }
-        const std::string name = seqDatabase.name(0);
-        const std::string backbone = seqDatabase.toString(0, true);
+        const std::string &name = bb.name, &backbone = bb.seq;
         const std::size_t partLen = opt.partLen;
         const std::size_t partNum = (backbone.size() + partLen - 1) / partLen;
         std::cout << "PartNum=" << partNum << std::endl;
@@ -912,8 +1145,6 @@ int main(int argc, char **argv) {
         if (backend != "hip" && backend != "wave" && backend != "flat" && backend != "host")
             throw std::runtime_error("PA_CNS_BACKEND must be hip, wave, flat, host or auto");
         const bool stageTimes = pagh::envInt("PA_CNS_STAGE_TIMES", 0) != 0;
-        using Clock = std::chrono::steady_clock;
-        const auto seconds = [](Clock::time_point a, Clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
         // Where the rows come from (the head of this file).  flat and device hand the graph stage flat arrays, so they need a
         // backend that takes them; device leaves the rows on the device, so it needs one that runs there.  No fallback to
         // another mode — but a file with a record that is not regular is read by the host ingest, whatever the mode.
@@ -970,19 +1201,7 @@ int main(int argc, char **argv) {
             for (std::size_t i; (i = next.fetch_add(1)) < partNum;) {
                 try {
                     auto &alns = alignments[i];
-                    {   // std::sort by score, descending: the same algorithm on a proxy array (the tie order is the library's)
-                        struct Proxy {
-                            unsigned score;
-                            std::size_t idx;
-                        };
-                        std::vector<Proxy> proxy(alns.size());
-                        for (std::size_t x = 0; x < alns.size(); ++x) proxy[x] = Proxy{alns[x].score, x};
-                        std::sort(proxy.begin(), proxy.end(), [](const Proxy &l, const Proxy &r) { return l.score > r.score; });
-                        std::vector<ScoredAln> sorted;
-                        sorted.reserve(std::min(alns.size(), opt.topK));
-                        for (std::size_t x = 0; x < proxy.size() && x < opt.topK; ++x) sorted.push_back(std::move(alns[proxy[x].idx]));
-                        alns.swap(sorted);
-                    }
+                    sortAndCut(alns, opt.topK);
                     const std::size_t left = i * partLen, right = std::min((i + 1) * partLen, backbone.size());
                     partWeights[i] = weightAln(alns, opt.alpha);
                     if (!onHost) continue;  // (the graphs of all parts are built together below)
@@ -1024,47 +1243,16 @@ int main(int argc, char **argv) {
         if (!onHost) {
             // the parts as flat arrays: every alignment's two rows in two pools, the regions of every part's graph sized from its
             // columns (include/pagraph_hip.h, pag_cns_consensus)
-            std::vector<pag_cns_part> parts(partNum);
+            HostRows hostRows;
+            if (!ingested) flattenParts(alignments, partWeights, hostRows);  // (no list here when the rows are in the pools already)
+            std::vector<pag_cns_part> parts;
+            parts.reserve(partNum);
+            sizeParts(backbone.size(), partLen, ingested ? ing.partFirst : hostRows.partFirst, ingested ? ing.nIns : hostRows.nIns,
+                      ingested ? ing.nEdgeCols : hostRows.nEdgeCols, 0, 0, parts);
             std::vector<pag_cns_aln> flat;
-            std::string qpool, tpool;
-            std::uint64_t outBytes = 0;
-            for (std::size_t i = 0; i < partNum; ++i) {
-                const std::size_t left = i * partLen, right = std::min((i + 1) * partLen, backbone.size());
-                pag_cns_part &P = parts[i];
-                P.bb_off = left;
-                P.bb_len = static_cast<std::uint32_t>(right - left);
-                P.aln_first = ingested ? ing.partFirst[i] : flat.size();
-                std::uint64_t nIns = ingested ? ing.nIns[i] : 0, nEdgeCols = ingested ? ing.nEdgeCols[i] : 0;
-                const auto &alns = alignments[i];
-                for (std::size_t x = 0; x < partWeights[i].size(); ++x) {  // (no list here when the rows are in the pools already)
-                    const Aln &a = alns[x].aln;
-                    pag_cns_aln f{};
-                    f.str_off = qpool.size();
-                    f.len = static_cast<std::uint32_t>(a.qstr.size());
-                    f.start = a.start;
-                    f.weight = static_cast<std::int32_t>(partWeights[i][x]);
-                    flat.push_back(f);
-                    qpool += a.qstr;
-                    tpool += a.tstr;
-                    for (std::size_t c = 0; c < a.qstr.size(); ++c) {
-                        const char qb = a.qstr[c], tb = a.tstr[c];
-                        if (qb != '-' && tb == '-') ++nIns;
-                        if (qb != '-') ++nEdgeCols;
-                    }
-                }
-                std::vector<ScoredAln>().swap(alignments[i]);  // (its rows live in the pools now)
-                P.n_aln = static_cast<std::uint32_t>(ingested ? ing.partFirst[i + 1] - ing.partFirst[i] : flat.size() - P.aln_first);
-                const std::uint64_t nodeCap = P.bb_len + 2ull + nIns, edgeCap = P.bb_len + 1ull + nEdgeCols + P.n_aln + 4096ull;
-                if (nodeCap > 0x7FFFFFFFull || edgeCap > 0x7FFFFFFFull) throw std::runtime_error("pa_cns: a part with more than 2^31 graph slots");
-                P.node_cap = static_cast<std::uint32_t>(nodeCap);
-                P.edge_cap = static_cast<std::uint32_t>(edgeCap);
-                P.aux_cap = static_cast<std::uint32_t>(std::min<std::uint64_t>(4 * nodeCap + 2048, 0x7FFFFFFFull));
-                P.out_cap = P.node_cap;
-                outBytes += P.out_cap;
-            }
-            if (ingested) flat.swap(ing.flat);
-            const char *qrows = ingested ? ing.qpool.get() : qpool.data(), *trows = ingested ? ing.tpool.get() : tpool.data();  // (null: the rows are on the device)
-            const std::uint64_t poolBytes = ingested ? ing.poolBytes : qpool.size();
+            flat.swap(ingested ? ing.flat : hostRows.flat);
+            const char *qrows = ingested ? ing.qpool.get() : hostRows.qpool.data(), *trows = ingested ? ing.tpool.get() : hostRows.tpool.data();  // (null: the rows are on the device)
+            const std::uint64_t poolBytes = ingested ? ing.poolBytes : hostRows.qpool.size();
             if (dumpRows) {
                 std::vector<char> fq, ft;
                 if (ingested && ing.dev) {  // (a verification aid: the rows come back for the dump alone)
@@ -1079,93 +1267,35 @@ int main(int argc, char **argv) {
                         dumpLine(dumpText[i], i, flat[a].start, flat[a].weight, dq + flat[a].str_off, dt + flat[a].str_off, flat[a].len);
                 });
             }
-            std::vector<char> outBuf(outBytes + 16);
-            std::vector<std::uint64_t> outOff(partNum + 1, 0);
-            std::vector<std::uint32_t> outLen(partNum, 0);
-            std::vector<std::int32_t> partErr(partNum, 0);
+            GraphIo io;
+            io.backbone = backbone.data();
+            io.backboneLen = backbone.size();
+            io.parts = &parts;
+            io.flat = &flat;
+            io.qrows = qrows;
+            io.trows = trows;
+            io.poolBytes = poolBytes;
+            io.dev = ingested ? ing.dev : nullptr;  // (the rows are where the kernels read them: no pool is uploaded)
+            io.prepare();
             std::atomic<long long> phaseNs[3] = {{0}, {0}, {0}};  // flat under PA_CNS_STAGE_TIMES: add_aln, merge_nodes, best_path + trim
             auto tGraph = Clock::now();
             if (backend == "hip" || backend == "wave") {
                 if (!hip) hip.reset(new HipLibrary());  // (throws when the library is missing; the call fails without a gfx950 device: there is no silent fallback)
-                const bool wave = backend == "wave";
                 if (stageTimes) {  // (the HIP runtime's start and the code object's load stay out of the stage's clock)
                     (void)hip->device_available();
                     tGraph = Clock::now();
                 }
-                const bool onDevice = ingested && ing.dev;  // (the rows are where the kernels read them: no pool is uploaded)
-                const int rc = onDevice ? hip->consensus_rows(device, wave ? 1 : 0, backbone.data(), backbone.size(), parts.data(), partNum, flat.data(), flat.size(), ing.dev,
-                                                              0, outBuf.data(), outBytes, outOff.data(), outLen.data(), partErr.data())
-                                        : (wave ? hip->consensus_wave : hip->consensus)(device, backbone.data(), backbone.size(), parts.data(), partNum, flat.data(),
-                                                                                        flat.size(), qrows, trows, poolBytes, 0, outBuf.data(), outBytes, outOff.data(),
-                                                                                        outLen.data(), partErr.data());
-                if (ing.dev) {
-                    hip->rows_free(ing.dev);
-                    ing.dev = nullptr;
-                }
-                if (rc != 0)
-                    throw std::runtime_error(std::string(onDevice ? "pag_cns_consensus_rows" : wave ? "pag_cns_consensus_wave" : "pag_cns_consensus") + " failed (" +
-                                             std::to_string(rc) + "): " + hip->last_error());
-            } else {  // the device's code on host threads
-                std::uint64_t oo = 0;
-                for (std::size_t i = 0; i < partNum; ++i) {
-                    outOff[i] = oo;
-                    oo += parts[i].out_cap;
-                }
-                outOff[partNum] = oo;
-                std::atomic<std::size_t> nextPart(0);
-                auto flatWork = [&]() {
-                    for (std::size_t i; (i = nextPart.fetch_add(1)) < partNum;) {
-                        const pag_cns_part &S = parts[i];
-                        std::vector<std::uint8_t> nb(S.node_cap), nf(S.node_cap), ev(S.edge_cap);
-                        std::vector<std::int32_t> ncov(S.node_cap), nw(S.node_cap), nbest(S.node_cap), ec(S.edge_cap);
-                        std::vector<std::uint32_t> nu[7], eu[6], aux(S.aux_cap);
-                        for (auto &v : nu) v.resize(S.node_cap);
-                        for (auto &v : eu) v.resize(S.edge_cap);
-                        std::vector<float> nscore(S.node_cap);
-                        pagcns::Arrays A{nb.data(), nf.data(), ncov.data(), nw.data(), nu[0].data(), nu[1].data(), nu[2].data(), nu[3].data(), nu[4].data(), nu[5].data(),
-                                         nu[6].data(), nscore.data(), nbest.data(), eu[0].data(), eu[1].data(), eu[2].data(), eu[3].data(), eu[4].data(), eu[5].data(),
-                                         ec.data(), ev.data(), aux.data()};
-                        pagcns::Part P{};
-                        P.bb_off = S.bb_off;
-                        P.bb_len = S.bb_len;
-                        P.n_aln = S.n_aln;
-                        P.aln_first = S.aln_first;
-                        P.out_off = outOff[i];
-                        P.node_cap = S.node_cap;
-                        P.edge_cap = S.edge_cap;
-                        P.aux_cap = S.aux_cap;
-                        P.out_cap = S.out_cap;
-                        static_assert(sizeof(pag_cns_aln) == sizeof(pagcns::Aln), "pag_cns_aln is pagcns::Aln");
-                        std::uint32_t len = 0;
-                        const auto *fa = reinterpret_cast<const pagcns::Aln *>(flat.data());
-                        if (!stageTimes) {
-                            partErr[i] = pagcns::run_part(A, P, backbone.data(), fa, qrows, trows, 0, outBuf.data(), &len);
-                        } else {  // run_part's steps with a clock between them
-                            pagcns::Graph g;
-                            pagcns::bind(g, A, P);
-                            const auto t0 = Clock::now();
-                            pagcns::init_backbone(g, backbone.data() + P.bb_off, P.bb_len);
-                            for (std::uint32_t a = 0; a < P.n_aln && !g.err; ++a) {
-                                const pagcns::Aln &al = fa[P.aln_first + a];
-                                pagcns::add_aln(g, qrows + al.str_off, trows + al.str_off, al.len, al.start, al.weight);
-                            }
-                            const auto t1 = Clock::now();
-                            if (!g.err) pagcns::merge_nodes(g);
-                            const auto t2 = Clock::now();
-                            if (!g.err) pagcns::consensus(g, 0, outBuf.data() + P.out_off, P.out_cap, &len);
-                            const auto t3 = Clock::now();
-                            phaseNs[0] += std::chrono::duration_cast<std::chrono::nanoseconds>(t1 - t0).count();
-                            phaseNs[1] += std::chrono::duration_cast<std::chrono::nanoseconds>(t2 - t1).count();
-                            phaseNs[2] += std::chrono::duration_cast<std::chrono::nanoseconds>(t3 - t2).count();
-                            partErr[i] = g.err;
-                        }
-                        outLen[i] = partErr[i] ? 0 : len;
+                struct FreeRows {  // (the device rows are released whether the call succeeds or not)
+                    HipLibrary &hip;
+                    Ingested &ing;
+                    ~FreeRows() {
+                        if (ing.dev) hip.rows_free(ing.dev);
+                        ing.dev = nullptr;
                     }
-                };
-                std::vector<std::thread> pool;
-                for (unsigned t = 1; t < nThreads; ++t) pool.emplace_back(flatWork);
-                flatWork();
-                for (auto &t : pool) t.join();
+                } freeRows{*hip, ing};
+                runDeviceBackend(*hip, backend == "wave", device, io);
+            } else {
+                runFlatBackend(io, nThreads, stageTimes, phaseNs);
             }
             if (stageTimes) {
                 std::cerr << "pa_cns: graph stage (" << backend << ") " << seconds(tGraph, Clock::now()) << " s" << std::endl;
@@ -1174,10 +1304,9 @@ int main(int argc, char **argv) {
                               << phaseNs[2] * 1e-9 << std::endl;
             }
             for (std::size_t i = 0; i < partNum; ++i) {
-                if (partErr[i] == pagcns::CNS_E_OVERRUN) throw std::runtime_error("pa_cns: an alignment runs past the end of its part");
-                if (partErr[i]) throw std::runtime_error("pa_cns: part " + std::to_string(i) + " ran out of its graph regions (code " + std::to_string(partErr[i]) + ")");
-                consensusResults[i].assign(outBuf.data() + outOff[i], outLen[i]);
-                consensusLen += outLen[i];
+                if (io.err[i]) throw std::runtime_error(partFailure(i, io.err[i]));
+                consensusResults[i].assign(io.buf.data() + io.off[i], io.len[i]);
+                consensusLen += io.len[i];
             }
         }
         if (dumpRows) {  // part start weight qrow trow, a line per kept alignment, parts in order, alignments in final order
@@ -1188,20 +1317,278 @@ int main(int argc, char **argv) {
         std::cout << consensusLen << std::endl;
         std::cout << backbone.size() << std::endl;
         std::ofstream of(opt.out);
-        std::string text;
-        text.reserve(backbone.size() + backbone.size() / 70 + name.size() + 8);
-        text += ">" + name + "\n";
-        std::size_t cnt = 0;
-        for (auto &seq : consensusResults)
-            for (char ch : seq) {
-                text += ch;
-                if (++cnt % 70 == 0) {
-                    text += '\n';
-                    cnt = 0;
-                }
+        of << fastaText(name, backbone.size(), consensusResults);
+        return 0;
+    } catch (const std::exception &e) {
+        std::cerr << "pa_cns: " << e.what() << std::endl;
+        return 1;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// --batch: the jobs of a manifest in one run.  The pipeline calls pa_cns once per new contig (AlignGraph2.py:500-510), a few
+// hundred parts each; the device backends pay from thousands of parts on, and every call pays its own start.  Here whole jobs
+// are gathered into GROUPS; a group's parts go to the backend in ONE call: the backbones one after the other, one pool pair,
+// bb_off / aln_first / str_off rebased.  Every job's output file and stdout lines are what its single run writes.
+//
+// Host memory: all backbones are loaded before any work (a byte a base, released as their group is built), and at most two
+// groups are alive — the one on the device and the one being ingested.  A group closes once it holds PA_CNS_BATCH_PARTS parts
+// (default kBatchParts) or its two row pools hold PA_CNS_BATCH_BYTES bytes together (default kBatchBytes), so a group holds at
+// most the limit plus one job; while a pool grows it may transiently hold twice that.  The length of the manifest does not enter.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr std::size_t kBatchParts = 4096;            // (1 000 parts leave the device three quarters empty, profiles/r07_pa_cns_wave_timing.json)
+constexpr std::uint64_t kBatchBytes = 8ull << 30;    // both pools of a group together
+// total parts of a batch from which its `auto` is `wave`.  Not the single run's 4 096: on 16 CPUs the whole program under `flat`
+// is ahead at 250 parts (2.56 s against 2.79 s) and `wave` from 491 on (4.01 s against 4.34 s), 8.8 s against 12.4 s at 1 601
+// (profiles/pa_cns_batch_timing.json); the two cross near 350, the constant stays on flat's side of it.
+constexpr std::size_t kBatchDevicePartsMin = 400;
+
+struct BatchJob {
+    std::size_t line = 0;  // of the manifest, 1-based
+    std::string in, align, out;
+    Backbone bb;
+    std::size_t bbLen = 0, partNum = 0;
+};
+// a failure of one job: what() starts with the job's backbone path
+struct JobFailure : std::runtime_error {
+    using std::runtime_error::runtime_error;
+};
+
+struct Group {
+    std::size_t firstJob = 0, nJobs = 0;
+    std::string backbone, qpool, tpool;  // the jobs' backbones and row pools, one after the other
+    std::vector<pag_cns_aln> flat;
+    std::vector<pag_cns_part> parts;           // by estimated cost, heaviest first
+    std::vector<std::uint32_t> jobOf, partOf;  // parts[k] is part partOf[k] of job firstJob + jobOf[k]
+    double sIngest = 0;
+    Clock::time_point ready;
+};
+
+// the jobs from `first` on, ingested one after the other (each on all host threads) until the group closes
+Group buildGroup(std::vector<BatchJob> &jobs, std::size_t first, const Options &opt, bool flatIngest, std::size_t limitParts, std::uint64_t limitBytes, bool stageTimes) {
+    const auto t0 = Clock::now();
+    Group g;
+    g.firstJob = first;
+    std::vector<pag_cns_part> parts;  // in manifest order
+    std::vector<std::uint32_t> jobOf, partOf;
+    for (std::size_t j = first; j < jobs.size(); ++j) {
+        BatchJob &job = jobs[j];
+        try {
+            Ingested ing;
+            HostRows host;
+            bool ingested = false;
+            if (flatIngest) {
+                std::string why;
+                ingested = ingestParallel(job.align, job.bb.seq, opt.partLen, opt.topK, opt.alpha, nullptr, 0, ing, why);
+                if (!ingested && stageTimes) std::cerr << "pa_cns: ingest (flat) falls back to the host ingest for " + job.align + ": " + why + "\n";
             }
-        if (cnt > 0) text += '\n';
-        of << text;
+            if (!ingested) {  // a file with a record that is not regular (or PA_CNS_INGEST=host): the host ingest, for this job alone
+                auto alignments = readFromRefFile(job.align, job.bb.seq, opt.partLen);
+                std::vector<std::vector<std::size_t>> partWeights(job.partNum);
+                pagh::parallelFor(job.partNum, 1, [&](std::size_t i) {
+                    sortAndCut(alignments[i], opt.topK);
+                    partWeights[i] = weightAln(alignments[i], opt.alpha);
+                });
+                flattenParts(alignments, partWeights, host);
+            }
+            const std::uint64_t bbBase = g.backbone.size(), alnBase = g.flat.size(), strBase = g.qpool.size();
+            sizeParts(job.bbLen, opt.partLen, ingested ? ing.partFirst : host.partFirst, ingested ? ing.nIns : host.nIns, ingested ? ing.nEdgeCols : host.nEdgeCols, bbBase,
+                      alnBase, parts);
+            for (std::size_t i = 0; i < job.partNum; ++i) {
+                jobOf.push_back(static_cast<std::uint32_t>(j - first));
+                partOf.push_back(static_cast<std::uint32_t>(i));
+            }
+            const std::vector<pag_cns_aln> &flat = ingested ? ing.flat : host.flat;
+            g.flat.reserve(g.flat.size() + flat.size());
+            for (pag_cns_aln f : flat) {
+                f.str_off += strBase;
+                g.flat.push_back(f);
+            }
+            g.backbone += job.bb.seq;
+            std::string().swap(job.bb.seq);
+            if (ingested) {
+                g.qpool.append(ing.qpool.get(), ing.poolBytes);
+                g.tpool.append(ing.tpool.get(), ing.poolBytes);
+            } else {
+                g.qpool += host.qpool;
+                g.tpool += host.tpool;
+            }
+        } catch (const std::exception &e) {
+            throw JobFailure(job.in + ": " + e.what());
+        }
+        ++g.nJobs;
+        if (parts.size() >= limitParts || g.qpool.size() + g.tpool.size() >= limitBytes) break;
+    }
+    // Heaviest first: the kernel's grid takes blocks in array order, and a group's run time ends with its slowest part.  The
+    // estimate is the part's alignment columns plus its backbone; ties keep manifest order, then part order (the sort is stable).
+    std::vector<std::uint64_t> cost(parts.size());
+    for (std::size_t k = 0; k < parts.size(); ++k) {
+        cost[k] = parts[k].bb_len;
+        for (std::uint64_t a = parts[k].aln_first; a < parts[k].aln_first + parts[k].n_aln; ++a) cost[k] += g.flat[a].len;
+    }
+    std::vector<std::size_t> order(parts.size());
+    std::iota(order.begin(), order.end(), std::size_t(0));
+    std::stable_sort(order.begin(), order.end(), [&](std::size_t l, std::size_t r) { return cost[l] > cost[r]; });
+    g.parts.reserve(parts.size());
+    for (std::size_t k : order) {
+        g.parts.push_back(parts[k]);
+        g.jobOf.push_back(jobOf[k]);
+        g.partOf.push_back(partOf[k]);
+    }
+    // (the kernels index the arrays by what the parts say: every range is checked here, before anything runs on them)
+    for (const pag_cns_part &P : g.parts) {
+        bool ok = P.bb_off + P.bb_len <= g.backbone.size() && P.aln_first + P.n_aln <= g.flat.size();
+        for (std::uint64_t a = P.aln_first; ok && a < P.aln_first + P.n_aln; ++a) ok = g.flat[a].str_off + g.flat[a].len <= g.qpool.size();
+        if (!ok) throw std::logic_error("pa_cns: a part of the group reaches out of the group's arrays");
+    }
+    g.ready = Clock::now();
+    g.sIngest = seconds(t0, g.ready);
+    return g;
+}
+
+std::vector<BatchJob> readManifest(const std::string &path) {
+    std::ifstream in(path);
+    if (!in.is_open()) throw std::runtime_error("--batch: cannot read " + path);
+    std::vector<BatchJob> jobs;
+    std::map<std::string, std::size_t> outputs;
+    std::string text;
+    for (std::size_t line = 1; std::getline(in, text); ++line) {
+        if (!text.empty() && text.back() == '\r') text.pop_back();
+        if (text.empty()) continue;
+        std::vector<std::string> fields(1);
+        for (char c : text) {
+            if (c == '\t') fields.emplace_back();
+            else fields.back() += c;
+        }
+        bool ok = fields.size() == 3;
+        for (const std::string &f : fields) ok = ok && !f.empty();
+        if (!ok)
+            throw std::runtime_error(path + " line " + std::to_string(line) + ": a job is three TAB-separated fields (backbone, alignments, output), this line has " +
+                                     std::to_string(fields.size()) + (fields.size() == 3 ? ", one of them empty" : ""));
+        const auto seen = outputs.emplace(fields[2], line);
+        if (!seen.second)
+            throw std::runtime_error(path + " line " + std::to_string(line) + ": the output " + fields[2] + " is the output of line " + std::to_string(seen.first->second) + " already");
+        BatchJob job;
+        job.line = line;
+        job.in = fields[0];
+        job.align = fields[1];
+        job.out = fields[2];
+        jobs.push_back(std::move(job));
+    }
+    return jobs;
+}
+
+int runBatch(const Options &opt) {
+    try {
+        // what a batch cannot run under, before any work
+        const char *backendEnv = std::getenv("PA_CNS_BACKEND");
+        std::string backend = backendEnv ? backendEnv : "auto";
+        if (backend == "host") throw std::runtime_error("--batch hands the graph stage flat rows, which PA_CNS_BACKEND=host does not take: flat, wave, hip or auto");
+        if (backend != "hip" && backend != "wave" && backend != "flat" && backend != "auto") throw std::runtime_error("PA_CNS_BACKEND must be hip, wave, flat, host or auto");
+        const char *ingestEnv = std::getenv("PA_CNS_INGEST");
+        const std::string ingest = ingestEnv ? ingestEnv : "flat";
+        if (ingest == "device")
+            throw std::runtime_error("--batch does not take PA_CNS_INGEST=device (its rows live in one device pool per file, a group's call takes one): flat or host");
+        if (ingest != "host" && ingest != "flat") throw std::runtime_error("PA_CNS_INGEST must be host, flat or device");
+        if (std::getenv("PA_CNS_DUMP_ROWS")) throw std::runtime_error("--batch does not take PA_CNS_DUMP_ROWS (the dump is one job's rows): run that job alone");
+        if (opt.partLen == 0) throw std::runtime_error("--batch needs a part length (-l) above 0");
+        const long long partsEnv = pagh::envInt("PA_CNS_BATCH_PARTS", static_cast<long long>(kBatchParts));
+        const long long bytesEnv = pagh::envInt("PA_CNS_BATCH_BYTES", static_cast<long long>(kBatchBytes));
+        if (partsEnv < 1 || bytesEnv < 1) throw std::runtime_error("PA_CNS_BATCH_PARTS and PA_CNS_BATCH_BYTES are numbers above 0");
+        const std::size_t limitParts = static_cast<std::size_t>(partsEnv);
+        const std::uint64_t limitBytes = static_cast<std::uint64_t>(bytesEnv);
+        const bool stageTimes = pagh::envInt("PA_CNS_STAGE_TIMES", 0) != 0;
+        std::vector<BatchJob> jobs = readManifest(opt.batch);
+
+        // all backbones first: a job without one ends the run before anything is written
+        std::size_t totalParts = 0;
+        for (BatchJob &job : jobs) {
+            if (!loadBackbone(job.in, job.bb)) {
+                std::cerr << "[Error] No backbone: " << job.in << std::endl;
+                return 2;
+            }
+            job.bbLen = job.bb.seq.size();
+            job.partNum = (job.bbLen + opt.partLen - 1) / opt.partLen;
+            totalParts += job.partNum;
+        }
+        const bool chosen = backend == "auto";
+        // (`wave` where the single run's auto names `hip`: every row of profiles/r07_pa_cns_wave_timing.json has it 2.5x ahead)
+        if (chosen) backend = totalParts >= kBatchDevicePartsMin ? "wave" : "flat";
+        if (stageTimes)
+            std::cerr << "pa_cns: batch of " << jobs.size() << " jobs, " << totalParts << " parts: backend " << backend << (chosen ? " (auto)" : "") << ", ingest " << ingest
+                      << std::endl;
+        const bool onDevice = backend != "flat";
+        const int device = static_cast<int>(pagh::envInt("PAGRAPH_DEVICE", 0));
+        std::unique_ptr<HipLibrary> hip;
+        if (onDevice && !jobs.empty()) {
+            hip.reset(new HipLibrary());       // (throws when the library is missing; the first call fails without a gfx950 device: no silent fallback)
+            (void)hip->device_available();     // (the HIP runtime's start stays out of the first group's clock)
+        }
+        const auto build = [&](std::size_t first) { return buildGroup(jobs, first, opt, ingest == "flat", limitParts, limitBytes, stageTimes); };
+
+        // Group after group.  With a device backend the next group is ingested on the host threads while this one's call is on the
+        // device; with `flat` the host threads are the backend, so the groups run one after the other.
+        std::future<Group> nextGroup;
+        if (onDevice && !jobs.empty()) nextGroup = std::async(std::launch::async, build, std::size_t(0));
+        for (std::size_t first = 0, gi = 0; first < jobs.size(); ++gi) {
+            const auto tWait = Clock::now();
+            Group g = onDevice ? nextGroup.get() : build(first);
+            const double sDeviceWaited = onDevice ? seconds(tWait, Clock::now()) : 0.0;
+            const double sIngestWaited = onDevice ? std::max(0.0, seconds(g.ready, tWait)) : 0.0;
+            first = g.firstJob + g.nJobs;
+            if (onDevice && first < jobs.size()) nextGroup = std::async(std::launch::async, build, first);
+            const BatchJob &head = jobs[g.firstJob];
+            const std::string groupName = head.in + (g.nJobs > 1 ? " (the first of a group of " + std::to_string(g.nJobs) + " jobs)" : "");
+
+            GraphIo io;
+            io.backbone = g.backbone.data();
+            io.backboneLen = g.backbone.size();
+            io.parts = &g.parts;
+            io.flat = &g.flat;
+            io.qrows = g.qpool.data();
+            io.trows = g.tpool.data();
+            io.poolBytes = g.qpool.size();
+            io.prepare();
+            std::atomic<long long> phaseNs[3] = {{0}, {0}, {0}};
+            const auto tGraph = Clock::now();
+            try {
+                if (onDevice) {
+                    runDeviceBackend(*hip, backend == "wave", device, io);
+                } else {
+                    const unsigned nThreads = std::max(1u, std::min<unsigned>(std::max(1u, pagh::usableCpus()), static_cast<unsigned>(std::max<std::size_t>(1, g.parts.size()))));
+                    runFlatBackend(io, nThreads, stageTimes, phaseNs);
+                }
+            } catch (const std::exception &e) {
+                throw JobFailure(groupName + ": " + e.what());
+            }
+            const double sGraph = seconds(tGraph, Clock::now());
+            if (stageTimes)
+                std::cerr << "pa_cns: group " << gi << ": jobs " << g.nJobs << " parts " << g.parts.size() << " ingest " << g.sIngest << " s graph stage (" << backend << ") "
+                          << sGraph << " s device waited " << sDeviceWaited << " s ingest waited " << sIngestWaited << " s" << std::endl;
+
+            // back to the jobs by index; a failing part ends the run before anything of this group is written
+            std::vector<std::vector<std::string>> results(g.nJobs);
+            for (std::size_t j = 0; j < g.nJobs; ++j) results[j].resize(jobs[g.firstJob + j].partNum);
+            std::size_t badK = SIZE_MAX;
+            for (std::size_t k = 0; k < g.parts.size(); ++k) {
+                if (io.err[k]) {  // (the first in manifest order, then part order)
+                    if (badK == SIZE_MAX || std::make_pair(g.jobOf[k], g.partOf[k]) < std::make_pair(g.jobOf[badK], g.partOf[badK])) badK = k;
+                    continue;
+                }
+                results[g.jobOf[k]][g.partOf[k]].assign(io.buf.data() + io.off[k], io.len[k]);
+            }
+            if (badK != SIZE_MAX) throw JobFailure(jobs[g.firstJob + g.jobOf[badK]].in + ": " + partFailure(g.partOf[badK], io.err[badK]));
+            for (std::size_t j = 0; j < g.nJobs; ++j) {
+                const BatchJob &job = jobs[g.firstJob + j];
+                std::size_t consensusLen = 0;
+                for (const std::string &s : results[j]) consensusLen += s.size();
+                std::cout << "PartNum=" << job.partNum << std::endl;
+                std::cout << consensusLen << std::endl;
+                std::cout << job.bbLen << std::endl;
+                std::ofstream of(job.out);
+                of << fastaText(job.bb.name, job.bbLen, results[j]);
+            }
+        }
         return 0;
     } catch (const std::exception &e) {
         std::cerr << "pa_cns: " << e.what() << std::endl;
