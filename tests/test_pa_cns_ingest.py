@@ -65,6 +65,20 @@ def test_flat_ingest_rows_on_the_seeded_file(case, tmp_path):
         assert r.returncode == 0 and r.stdout == stdout and ref_fasta == fasta
 
 
+@pytest.mark.parametrize("name", list(cns_cases.CASES))
+def test_host_backend_dumps_the_rows_the_flat_backend_gets(name, tmp_path):
+    # the dump is one thing whichever backend builds the graphs: the host backend's, from its lists, is the flat backend's, from
+    # the flattened rows of the same host ingest
+    case = cns_cases.CASES[name]
+    d = cns_cases.write_case(case, str(tmp_path))
+    rh, fasta_h, dump_h = ic.run(EXE, d, "host", case, ingest="host", backend="host")
+    rf, fasta_f, dump_f = ic.run(EXE, d, "flat", case, ingest="host", backend="flat")
+    assert rh.returncode == 0 and rf.returncode == 0, (rh.stderr[-500:], rf.stderr[-500:])
+    assert "graph stage (host, with the per-part sort)" in rh.stderr, rh.stderr[-500:]
+    assert dump_h and dump_f == dump_h, "the rows the host backend dumps differ from the flat backend's"
+    assert fasta_h and fasta_f == fasta_h and rf.stdout == rh.stdout
+
+
 def _case_with_extra_record(tmp_path, extra):
     case = cns_cases.CASES["three_parts_ties"]
     d = cns_cases.write_case(case, str(tmp_path))
