@@ -303,6 +303,7 @@ SIGNATURES = {
     "pag_debug_trav_vertices": (_int, [_vp, _vp, _vp]),
     "pag_debug_stream_sizes": (_int, [_vp, _u64p, _u64p]),
     "pag_debug_streams": (_int, [_vp, _vp, _vp, _vp, _vp]),
+    "pag_debug_slot_grow": (_int, [_vp, _vp, _u32, _vp, _vp, _u64]),
     "pag_debug_cov_filter": (_int, [_vp, _u64, _vp, _u64, _u32, _vp, _int]),
     "pag_debug_predicates": (_int, [_vp, _u64, _f64, _vp, _vp, _int]),
     "pag_debug_predicates_tab": (_int, [_vp, _u64, _f64, _vp, _vp, _int, _vp]),

@@ -18,6 +18,7 @@
 #include <map>
 #include <vector>
 
+#include "dev_call.hpp"
 #include "pag_device.hpp"
 
 namespace pagdev {
@@ -107,55 +108,31 @@ extern "C" int pag_kmer_count(const pag_seqs *reads, int reads_on_device, uint32
         set_error("pag_kmer_count: bad arguments (k must be 1..16)");
         return PAG_EINVAL;
     }
-    PAG_HIP_TRY(hipSetDevice(device));
     const uint64_t n_codes = 1ull << (2 * k);
     const uint64_t n_words = (n_codes + 31) / 32;
-    hipStream_t s = nullptr;
     uint32_t *table = nullptr, *d_bitmap = nullptr, *d_len = nullptr;
     uint64_t *d_off = nullptr;
     uint8_t *d_packed = nullptr;
     unsigned long long *d_hist = nullptr;
-    std::vector<void *> owned;
-    auto cleanup = [&]() {
-        for (void *p : owned) hipFree(p);
-        if (s) hipStreamDestroy(s);
-    };
-#define KC_TRY(expr)                                                                              \
-    do {                                                                                          \
-        hipError_t e__ = (expr);                                                                  \
-        if (e__ != hipSuccess) {                                                                  \
-            set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-            cleanup();                                                                            \
-            return PAG_EFAULT;                                                                    \
-        }                                                                                         \
-    } while (0)
-    KC_TRY(hipStreamCreate(&s));
-    KC_TRY(hipMalloc((void **)&table, std::max<uint64_t>(n_codes, 32) * 4));
-    owned.push_back(table);
-    KC_TRY(hipMalloc((void **)&d_hist, (KC_BINS + 8) * 8));
-    owned.push_back(d_hist);
-    KC_TRY(hipMemsetAsync(table, 0, std::max<uint64_t>(n_codes, 32) * 4, s));
-    KC_TRY(hipMemsetAsync(d_hist, 0, (KC_BINS + 8) * 8, s));
+    DevCall D("pag_kmer_count");  // (a blocking stream: the plain hipMemcpy below come after its kernels; the device stays current)
+    int rc = D.open(device, false, hipStreamDefault);
+    if (rc || (rc = D.alloc(&table, std::max<uint64_t>(n_codes, 32))) || (rc = D.alloc(&d_hist, KC_BINS + 8))) return rc;
+    const hipStream_t s = D.s;
+    PAG_HIP_TRY(hipMemsetAsync(table, 0, std::max<uint64_t>(n_codes, 32) * 4, s));
+    PAG_HIP_TRY(hipMemsetAsync(d_hist, 0, (KC_BINS + 8) * 8, s));
     const uint64_t n_reads = reads->n_seqs;
     if (reads_on_device) {
         d_off = (uint64_t *)reads->byte_off;
         d_len = (uint32_t *)reads->len;
         d_packed = (uint8_t *)reads->packed;  // the caller guarantees 8 readable bytes past every read (pag_seqs contract)
     } else if (n_reads) {
-        KC_TRY(hipMalloc((void **)&d_off, n_reads * 8));
-        owned.push_back(d_off);
-        KC_TRY(hipMalloc((void **)&d_len, n_reads * 4));
-        owned.push_back(d_len);
-        KC_TRY(hipMalloc((void **)&d_packed, reads->packed_bytes + 64));
-        owned.push_back(d_packed);
-        KC_TRY(hipMemcpyAsync(d_off, reads->byte_off, n_reads * 8, hipMemcpyHostToDevice, s));
-        KC_TRY(hipMemcpyAsync(d_len, reads->len, n_reads * 4, hipMemcpyHostToDevice, s));
-        KC_TRY(hipMemsetAsync(d_packed + reads->packed_bytes, 0, 64, s));
-        KC_TRY(hipMemcpyAsync(d_packed, reads->packed, reads->packed_bytes, hipMemcpyHostToDevice, s));
+        if ((rc = D.up(reads->byte_off, n_reads, &d_off, 0)) || (rc = D.up(reads->len, n_reads, &d_len, 0)) ||
+            (rc = D.up(reads->packed, reads->packed_bytes, &d_packed, 64)))
+            return rc;
     }
     hipEvent_t ev[3];
-    for (auto &e : ev) KC_TRY(hipEventCreate(&e));
-    KC_TRY(hipEventRecord(ev[0], s));
+    for (auto &e : ev) PAG_HIP_TRY(hipEventCreate(&e));
+    PAG_HIP_TRY(hipEventRecord(ev[0], s));
     if (n_reads) {
         const unsigned grid = (unsigned)std::min<uint64_t>(n_reads, 1u << 20);
         // The table is filled one slice of the code range per launch once it is larger than the Infinity Cache can hold beside
@@ -171,10 +148,10 @@ extern "C" int pag_kmer_count(const pag_seqs *reads, int reads_on_device, uint32
     }
     // d_hist: [0, KC_BINS) the histogram, [KC_BINS + 1] the solid count (kc_select), [KC_BINS + 2] the k-mers counted
     kc_hist<<<dim3(4096), dim3(256), 0, s>>>(table, n_codes, d_hist, d_hist + KC_BINS + 2);
-    KC_TRY(hipEventRecord(ev[1], s));
+    PAG_HIP_TRY(hipEventRecord(ev[1], s));
     std::vector<unsigned long long> hist(KC_BINS + 8);
-    KC_TRY(hipMemcpyAsync(hist.data(), d_hist, (KC_BINS + 8) * 8, hipMemcpyDeviceToHost, s));
-    KC_TRY(hipStreamSynchronize(s));
+    PAG_HIP_TRY(hipMemcpyAsync(hist.data(), d_hist, (KC_BINS + 8) * 8, hipMemcpyDeviceToHost, s));
+    PAG_HIP_TRY(hipStreamSynchronize(s));
 
     // the reference's rule (kmer_counter.cpp:59-77), same expression in double
     uint64_t min_abundance = 0;
@@ -191,7 +168,7 @@ extern "C" int pag_kmer_count(const pag_seqs *reads, int reads_on_device, uint32
         }
         if (!found && hist[KC_BINS - 1]) {  // the tail: exact abundances from the table itself
             std::vector<uint32_t> t(n_codes);
-            KC_TRY(hipMemcpy(t.data(), table, n_codes * 4, hipMemcpyDeviceToHost));
+            PAG_HIP_TRY(hipMemcpy(t.data(), table, n_codes * 4, hipMemcpyDeviceToHost));
             std::map<uint64_t, uint64_t> tail;
             for (uint64_t i = 0; i < n_codes; ++i)
                 if (t[i] >= KC_BINS - 1) ++tail[t[i]];
@@ -207,8 +184,7 @@ extern "C" int pag_kmer_count(const pag_seqs *reads, int reads_on_device, uint32
     if (bitmap_on_device) {
         d_bitmap = bitmap;
     } else {
-        KC_TRY(hipMalloc((void **)&d_bitmap, n_words * 4));
-        owned.push_back(d_bitmap);
+        if ((rc = D.alloc(&d_bitmap, n_words))) return rc;
     }
     unsigned long long *d_ns = d_hist + KC_BINS + 1;
     if (n_codes >= 32) {
@@ -216,7 +192,7 @@ extern "C" int pag_kmer_count(const pag_seqs *reads, int reads_on_device, uint32
             table, n_words, (uint32_t)std::min<uint64_t>(min_abundance, 0xFFFFFFFFull), d_bitmap, d_ns);
     } else {  // k <= 2: fewer than 32 codes, one word assembled on the host
         std::vector<uint32_t> t(32, 0);
-        KC_TRY(hipMemcpy(t.data(), table, n_codes * 4, hipMemcpyDeviceToHost));
+        PAG_HIP_TRY(hipMemcpy(t.data(), table, n_codes * 4, hipMemcpyDeviceToHost));
         uint32_t bits = 0;
         unsigned long long ns = 0;
         for (uint64_t i = 0; i < n_codes; ++i)
@@ -224,15 +200,15 @@ extern "C" int pag_kmer_count(const pag_seqs *reads, int reads_on_device, uint32
                 bits |= 1u << i;
                 ++ns;
             }
-        KC_TRY(hipMemcpy(d_bitmap, &bits, 4, hipMemcpyHostToDevice));
-        KC_TRY(hipMemcpy(d_ns, &ns, 8, hipMemcpyHostToDevice));
+        PAG_HIP_TRY(hipMemcpy(d_bitmap, &bits, 4, hipMemcpyHostToDevice));
+        PAG_HIP_TRY(hipMemcpy(d_ns, &ns, 8, hipMemcpyHostToDevice));
     }
-    KC_TRY(hipEventRecord(ev[2], s));
+    PAG_HIP_TRY(hipEventRecord(ev[2], s));
     unsigned long long ns = 0;
-    KC_TRY(hipMemcpyAsync(&ns, d_ns, 8, hipMemcpyDeviceToHost, s));
-    if (!bitmap_on_device) KC_TRY(hipMemcpyAsync(bitmap, d_bitmap, n_words * 4, hipMemcpyDeviceToHost, s));
-    KC_TRY(hipStreamSynchronize(s));
-    KC_TRY(hipGetLastError());
+    PAG_HIP_TRY(hipMemcpyAsync(&ns, d_ns, 8, hipMemcpyDeviceToHost, s));
+    if (!bitmap_on_device) PAG_HIP_TRY(hipMemcpyAsync(bitmap, d_bitmap, n_words * 4, hipMemcpyDeviceToHost, s));
+    PAG_HIP_TRY(hipStreamSynchronize(s));
+    PAG_HIP_TRY(hipGetLastError());
     if (res) {
         float ms = 0;
         res->min_abundance = min_abundance;
@@ -244,7 +220,5 @@ extern "C" int pag_kmer_count(const pag_seqs *reads, int reads_on_device, uint32
         res->ms_select = ms;
     }
     for (auto &e : ev) hipEventDestroy(e);
-    cleanup();
     return PAG_OK;
-#undef KC_TRY
 }

@@ -260,12 +260,12 @@ extern "C" int pag_render_dump_lines(const pag_path_node *records, uint64_t n, u
     }
     if (!pag_device_available()) return PAG_ENODEV;  // (no CPU fallback)
     if (n == 0) return PAG_OK;
-    TextCall b;
-    void *scratch = nullptr, *text = nullptr;
+    TextCall b("pag_render_dump_lines");
+    char *scratch = nullptr, *text = nullptr;
     int rc = b.begin(device, n, blob);
     if (rc || (rc = b.alloc(&scratch, text_scratch_bytes(n))) || (rc = b.upload(records, n, blob))) return rc;
-    const DumpTables T = dump_tables_at((const uint32_t *)b.tab, n_ctgs, n_refs);
-    const PathSrcRecords src{(const pag_path_node *)b.rec};
+    const DumpTables T = dump_tables_at(b.tab, n_ctgs, n_refs);
+    const PathSrcRecords src{b.rec};
     if ((rc = dump_measure(src, n, k, T, scratch, nullptr, b.s, 0))) return rc;
     uint64_t total = 0;
     PAG_HIP_TRY(hipMemcpyAsync(&total, (char *)scratch + 8, 8, hipMemcpyDeviceToHost, b.s));

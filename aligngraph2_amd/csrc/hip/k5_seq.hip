@@ -224,17 +224,17 @@ extern "C" int pag_render_path_sequence(const pag_path_node *records, uint64_t n
         set_error("pag_render_path_sequence: the sequence takes %llu bytes, the buffer holds %llu", (unsigned long long)total, (unsigned long long)cap);
         return PAG_ERANGE;
     }
-    TextCall b;
-    void *seqs = nullptr, *scratch = nullptr, *text = nullptr;
+    TextCall b("pag_render_path_sequence");
+    char *seqs = nullptr, *scratch = nullptr, *text = nullptr;
     int rc = b.begin(device, n, blob);
     if (rc || (rc = b.alloc(&seqs, seq_sources_bytes(ctgs, refs))) || (rc = b.alloc(&scratch, text_scratch_bytes(n))) || (rc = b.alloc(&text, total + 16)) ||
         (rc = b.upload(records, n, blob)))
         return rc;
     SeqSources S{};
     if ((rc = seq_sources_upload(seqs, ctgs, refs, &S, b.s))) return rc;
-    const DumpTables T = dump_tables_at((const uint32_t *)b.tab, ctgs->n_seqs, refs->n_seqs);
+    const DumpTables T = dump_tables_at(b.tab, ctgs->n_seqs, refs->n_seqs);
     const SeqParams P{k, deviation, error_rate};
-    const PathSrcRecords src{(const pag_path_node *)b.rec};
+    const PathSrcRecords src{b.rec};
     if ((rc = seq_measure(src, n, k, scratch, nullptr, b.s, 0))) return rc;
     if ((rc = seq_render(src, n, P, T, S, scratch, (char *)text, total, nullptr, b.s, 0))) return rc;
     uint64_t head[2] = {0, 0};  // [ticket, not renderable][total]

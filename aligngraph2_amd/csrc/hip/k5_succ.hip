@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "dev_call.hpp"
 #include "pag_device.hpp"
 #include "pagraph_debug.h"
 #include "pag_travel.hpp"
@@ -499,30 +500,17 @@ static int debug_predicates(const uint32_t *rows, uint64_t n, double err, uint8_
     using namespace pagdev;
     if (!rows || !grade || !edge_sim) return PAG_EINVAL;
     if (hipSetDevice(device) != hipSuccess) return PAG_ENODEV;
+    if (n == 0) return PAG_OK;
+    DevCall D("pag_debug_predicates");  // (the device stays current)
     uint32_t *d_rows = nullptr;
     uint8_t *d_out = nullptr;
-    if (n == 0) return PAG_OK;
-    PAG_HIP_TRY(hipMalloc((void **)&d_rows, n * 24));
-    if (hipMalloc((void **)&d_out, 2 * n + 16) != hipSuccess) {
-        hipFree(d_rows);
-        return PAG_ENOMEM;
-    }
+    int rc;
+    if ((rc = D.open(device, false, hipStreamDefault)) || (rc = D.up(rows, 6 * n, &d_rows, 0)) || (rc = D.alloc(&d_out, 2 * n, 16))) return rc;
     unsigned long long *d_cnt = (unsigned long long *)(d_out + ((2 * n + 7) & ~(uint64_t)7));
-    hipError_t e = hipMemcpy(d_rows, rows, n * 24, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(d_cnt, 0, 8);
-    if (e == hipSuccess) {
-        if (n_through_table) k_debug_predicates_tab<<<dim3((unsigned)((n + 255) / 256)), dim3(256)>>>(d_rows, n, err, d_out, d_out + n, d_cnt);
-        else k_debug_predicates<<<dim3((unsigned)((n + 255) / 256)), dim3(256)>>>(d_rows, n, err, d_out, d_out + n);
-        e = hipDeviceSynchronize();
-    }
-    if (e == hipSuccess && n_through_table) e = hipMemcpy(n_through_table, d_cnt, 8, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(grade, d_out, n, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(edge_sim, d_out + n, n, hipMemcpyDeviceToHost);
-    hipFree(d_rows);
-    hipFree(d_out);
-    if (e != hipSuccess) {
-        set_error("pag_debug_predicates: %s", hipGetErrorString(e));
-        return PAG_EFAULT;
-    }
-    return PAG_OK;
+    PAG_HIP_TRY(hipMemsetAsync(d_cnt, 0, 8, D.s));
+    if (n_through_table) k_debug_predicates_tab<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, D.s>>>(d_rows, n, err, d_out, d_out + n, d_cnt);
+    else k_debug_predicates<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, D.s>>>(d_rows, n, err, d_out, d_out + n);
+    if (n_through_table && (rc = D.down((unsigned long long *)n_through_table, (const unsigned long long *)d_cnt, 1))) return rc;
+    if ((rc = D.down(grade, (const uint8_t *)d_out, n)) || (rc = D.down(edge_sim, (const uint8_t *)d_out + n, n))) return rc;
+    return D.finish();
 }

@@ -1958,10 +1958,10 @@ namespace pagdev {
 // one internal buffer of a hook job: `bytes` bytes of `fill`, guard bytes behind them
 constexpr size_t HOOK_GUARD_BYTES = 64;
 constexpr int HOOK_GUARD_FILL = 0x5A;
-static int hook_guarded(HookDev &D, size_t bytes, int fill, void **out, std::vector<void *> &guards) {
-    void *p = nullptr;
-    PAG_HIP_TRY(hipMalloc(&p, bytes + HOOK_GUARD_BYTES));
-    D.bufs.push_back(p);
+static int hook_guarded(DevCall &D, size_t bytes, int fill, void **out, std::vector<void *> &guards) {
+    char *p = nullptr;
+    const int rc = D.alloc(&p, bytes, HOOK_GUARD_BYTES);
+    if (rc) return rc;
     if (bytes) PAG_HIP_TRY(hipMemsetAsync(p, fill, bytes, D.s));
     PAG_HIP_TRY(hipMemsetAsync((char *)p + bytes, HOOK_GUARD_FILL, HOOK_GUARD_BYTES, D.s));
     guards.push_back((char *)p + bytes);
@@ -2034,10 +2034,10 @@ extern "C" int pag_debug_walk(const pag_debug_trav_graph *g, const pag_debug_wal
         for (size_t i = 1; i < rg.size(); ++i)
             if (rg[i].first < rg[i - 1].second) return PAG_EINVAL;
     }
-    HookDev D;
+    DevCall D("test hook");
     TravGraph G;
     int rc;
-    if ((rc = D.open(device)) || (rc = hook_upload_graph(D, g, &G))) return rc;
+    if ((rc = D.open(device, true, hipStreamDefault)) || (rc = hook_upload_graph(D, g, &G))) return rc;
     // ---- contig records
     std::vector<TravContig> hc(n_ctgs);
     for (uint32_t c = 0; c < n_ctgs; ++c) {

@@ -22,6 +22,7 @@
 #include <unordered_set>
 #include <vector>
 
+#include "dev_call.hpp"
 #include "pag_graph_impl.hpp"
 #include "pagraph_debug.h"
 #include "walk_config.hpp"
@@ -68,7 +69,7 @@ const pag_path_node *pag_travel_path_oriented(const pag_graph *g, uint64_t ctg_i
     }
     if (len) *len = g->path_len[slot];
     if (slot < g->path_ptr.size() && g->path_ptr[slot]) return g->path_ptr[slot];
-    return g->path_store + g->path_off[slot];
+    return g->path_store.as<pag_path_node>() + g->path_off[slot];
 }
 
 // ... and its dump text when pag_travel was asked for it (PAG_TRAVEL_RENDER_DUMPS) and could render it
@@ -160,17 +161,20 @@ int pag_debug_view_region(pag_graph *g, const uint32_t *ctg_len, uint64_t n_ctgs
 // PABruijnGraph::successors for one vertex of the prepared view (PABruijnGraph.cpp:370-373 -> searchSuccessors :167-197), see pagraph_hip.h
 int64_t pag_successors(const pag_graph *g, uint32_t code, uint64_t pos, pag_succ *out, uint64_t cap) {
     if (!g || !g->tg_ready || (!out && cap)) return PAG_EINVAL;
-    PAG_HIP_TRY(hipSetDevice(g->device));
+    DevCall D("pag_successors");  // (on the handle's stream; the device stays current)
+    D.s = g->stream;
+    int rc = D.open(g->device, false, DevCall::NO_STREAM);
+    if (rc) return rc;
     if (g->view_pruned || g->regional) {
         set_error("pag_successors: the prepared view was cut for given traversals (pag_travel_prepare_for / a regional graph): its lists are restricted to what those traversals can examine");
         return PAG_ERANGE;
     }
-    void *d = nullptr;
+    char *d = nullptr;
     const uint64_t room = std::min<uint64_t>(cap, g->tg.n_succ);
-    PAG_HIP_TRY(hipMalloc(&d, 16 + room * sizeof(pag_succ)));
+    if ((rc = D.alloc(&d, room * sizeof(pag_succ), 16))) return rc;
     unsigned long long *d_n = (unsigned long long *)d;
-    void *d_recs = (char *)d + 16;
-    int rc = trav_successors_of(g->tg, code, pos, d_recs, room, d_n, g->stream);
+    void *d_recs = d + 16;
+    rc = trav_successors_of(g->tg, code, pos, d_recs, room, d_n, g->stream);
     unsigned long long n = 0;
     if (rc == PAG_OK && (hipMemcpyAsync(&n, d_n, 8, hipMemcpyDeviceToHost, g->stream) != hipSuccess || hipStreamSynchronize(g->stream) != hipSuccess)) rc = PAG_EFAULT;
     if (rc == PAG_OK && n == ~0ull) {
@@ -183,7 +187,6 @@ int64_t pag_successors(const pag_graph *g, uint32_t code, uint64_t pos, pag_succ
                hipMemcpy(out, d_recs, std::min<uint64_t>(n, room) * sizeof(pag_succ), hipMemcpyDeviceToHost) != hipSuccess) {
         rc = PAG_EFAULT;
     }
-    hipFree(d);
     return rc == PAG_OK ? (int64_t)n : rc;
 }
 

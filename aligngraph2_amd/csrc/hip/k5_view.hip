@@ -630,33 +630,15 @@ using namespace pagdev;
 // their own (the manner of pag_debug_owner_pick, k_owner_pick.hip)
 extern "C" int pag_debug_zone_bands(const uint64_t *tval, uint64_t T, const uint32_t *zones, uint32_t n_z, uint32_t *lo, uint32_t *hi, int device) {
     if ((T && !tval) || (n_z && (!zones || !lo || !hi))) return PAG_EINVAL;
-    int before = 0;
-    PAG_HIP_TRY(hipGetDevice(&before));
-    PAG_HIP_TRY(hipSetDevice(device));
-    void *d_val = nullptr, *d_z = nullptr, *d_lo = nullptr, *d_hi = nullptr;
-    hipStream_t s = nullptr;
-    auto run = [&]() -> int {
-        PAG_HIP_TRY(hipStreamCreate(&s));
-        PAG_HIP_TRY(hipMalloc(&d_val, T * 8 + 16));
-        PAG_HIP_TRY(hipMalloc(&d_z, (size_t)n_z * 8 + 16));
-        PAG_HIP_TRY(hipMalloc(&d_lo, (size_t)n_z * 4 + 16));
-        PAG_HIP_TRY(hipMalloc(&d_hi, (size_t)n_z * 4 + 16));
-        if (T) PAG_HIP_TRY(hipMemcpyAsync(d_val, tval, T * 8, hipMemcpyHostToDevice, s));
-        if (n_z) PAG_HIP_TRY(hipMemcpyAsync(d_z, zones, (size_t)n_z * 8, hipMemcpyHostToDevice, s));
-        const int r = trav_zone_bands((const uint64_t *)d_val, T, (const uint32_t *)d_z, n_z, (uint32_t *)d_lo, (uint32_t *)d_hi, s);
-        if (r != PAG_OK) return r;
-        if (n_z) PAG_HIP_TRY(hipMemcpyAsync(lo, d_lo, (size_t)n_z * 4, hipMemcpyDeviceToHost, s));
-        if (n_z) PAG_HIP_TRY(hipMemcpyAsync(hi, d_hi, (size_t)n_z * 4, hipMemcpyDeviceToHost, s));
-        PAG_HIP_TRY(hipStreamSynchronize(s));
-        return PAG_OK;
-    };
-    const int rc = run();
-    if (s) hipStreamSynchronize(s);
-    for (void *p : {d_val, d_z, d_lo, d_hi})
-        if (p) hipFree(p);
-    if (s) hipStreamDestroy(s);
-    hipSetDevice(before);
-    return rc;
+    DevCall D("pag_debug_zone_bands");
+    uint64_t *d_val = nullptr;
+    uint32_t *d_z = nullptr, *d_lo = nullptr, *d_hi = nullptr;
+    int rc;
+    if ((rc = D.open(device, true, hipStreamDefault)) || (rc = D.up(tval, T, &d_val, 16)) || (rc = D.up(zones, 2 * (uint64_t)n_z, &d_z, 16)) ||
+        (rc = D.alloc(&d_lo, n_z, 16)) || (rc = D.alloc(&d_hi, n_z, 16)))
+        return rc;
+    if ((rc = trav_zone_bands(d_val, T, d_z, n_z, d_lo, d_hi, D.s)) || (rc = D.down(lo, d_lo, n_z)) || (rc = D.down(hi, d_hi, n_z))) return rc;
+    return D.finish();
 }
 
 extern "C" int pag_debug_trav_compact(uint32_t k, const uint32_t *tkey, const uint64_t *tval, const uint32_t *tseg, const uint16_t *tcnt, uint64_t T,
@@ -669,110 +651,55 @@ extern "C" int pag_debug_trav_compact(uint32_t k, const uint32_t *tkey, const ui
     const uint64_t nn = counts[0], np = counts[1], ne = counts[2];
     if (nn > T || np > T || ne > E || T >= 0xFFFFFFF0ull || E >= 0xFFFFFFF0ull) return PAG_EINVAL;
     if ((np && (!vpos || !vcnt || !vnode)) || (nn && !ncode) || (ne && (!eto || !estep))) return PAG_EINVAL;
-    int before = 0;
-    PAG_HIP_TRY(hipGetDevice(&before));
-    PAG_HIP_TRY(hipSetDevice(device));
     const uint64_t n_words = ((1ull << (2 * k)) + 63) / 64;
     const size_t tmp_bytes = trav_compact_tmp_bytes(T, E, k, nn);
     const uint64_t n_civ = region ? region->n_ctg_iv : 0, n_riv = region ? region->n_ref_iv : 0;
-    void *d_tkey = nullptr, *d_tval = nullptr, *d_tseg = nullptr, *d_tcnt = nullptr, *d_ekey = nullptr, *d_eval = nullptr, *d_eseg = nullptr, *d_iv = nullptr,
-         *d_vpos = nullptr, *d_vcnt = nullptr, *d_vnode = nullptr, *d_ncode = nullptr, *d_npos = nullptr, *d_nedge = nullptr, *d_eto = nullptr, *d_estep = nullptr,
-         *d_bitmap = nullptr, *d_rank = nullptr, *d_tmp = nullptr;
-    hipStream_t s = nullptr;
-    auto run = [&]() -> int {
-        PAG_HIP_TRY(hipStreamCreate(&s));
-        PAG_HIP_TRY(hipMalloc(&d_tkey, T * 4 + 16));
-        PAG_HIP_TRY(hipMalloc(&d_tval, T * 8 + 16));
-        PAG_HIP_TRY(hipMalloc(&d_tseg, T * 4 + 16));
-        PAG_HIP_TRY(hipMalloc(&d_tcnt, T * 2 + 16));
-        PAG_HIP_TRY(hipMalloc(&d_ekey, E * 4 + 16));
-        PAG_HIP_TRY(hipMalloc(&d_eval, E * 8 + 16));
-        PAG_HIP_TRY(hipMalloc(&d_eseg, E * 4 + 16));
-        PAG_HIP_TRY(hipMalloc(&d_iv, (n_civ + n_riv + 4) * 8));
-        // (the sizes trav_prepare_graph gives the arrays of the traversal graph; the node arrays with room for a node per vertex:
-        // a slot wrongly taken for the first of its segment is then reported by the comparison, not written astray)
-        const uint64_t nn_room = std::max(nn, np);
-        PAG_HIP_TRY(hipMalloc(&d_ncode, (nn_room + 1) * 4));
-        PAG_HIP_TRY(hipMalloc(&d_npos, (nn_room + 2) * 4));
-        PAG_HIP_TRY(hipMalloc(&d_nedge, (nn_room + 2) * 4));
-        PAG_HIP_TRY(hipMalloc(&d_vpos, (np + 4) * 8));
-        PAG_HIP_TRY(hipMalloc(&d_vcnt, (np + 1) * 2));
-        PAG_HIP_TRY(hipMalloc(&d_vnode, (np + 1) * 4));
-        PAG_HIP_TRY(hipMalloc(&d_eto, (ne + 4) * 4));
-        PAG_HIP_TRY(hipMalloc(&d_estep, (ne + 4) * 4));
-        PAG_HIP_TRY(hipMalloc(&d_bitmap, n_words * 8));
-        PAG_HIP_TRY(hipMalloc(&d_rank, n_words * 4));
-        PAG_HIP_TRY(hipMalloc(&d_tmp, tmp_bytes));
-        PAG_HIP_TRY(hipMemsetAsync(d_npos, 0, (nn + 2) * 4, s));
-        if (T) {
-            PAG_HIP_TRY(hipMemcpyAsync(d_tkey, tkey, T * 4, hipMemcpyHostToDevice, s));
-            PAG_HIP_TRY(hipMemcpyAsync(d_tval, tval, T * 8, hipMemcpyHostToDevice, s));
-            PAG_HIP_TRY(hipMemcpyAsync(d_tseg, tseg, T * 4, hipMemcpyHostToDevice, s));
-            PAG_HIP_TRY(hipMemcpyAsync(d_tcnt, tcnt, T * 2, hipMemcpyHostToDevice, s));
-        }
-        if (E) {
-            PAG_HIP_TRY(hipMemcpyAsync(d_ekey, ekey, E * 4, hipMemcpyHostToDevice, s));
-            PAG_HIP_TRY(hipMemcpyAsync(d_eval, eval, E * 8, hipMemcpyHostToDevice, s));
-            PAG_HIP_TRY(hipMemcpyAsync(d_eseg, eseg, E * 4, hipMemcpyHostToDevice, s));
-        }
-        TravView tv{};
-        if (region) {
-            uint32_t *d = (uint32_t *)d_iv;
-            if (n_civ) PAG_HIP_TRY(hipMemcpyAsync(d, region->ctg_iv, n_civ * 8, hipMemcpyHostToDevice, s));
-            if (n_riv) PAG_HIP_TRY(hipMemcpyAsync(d + 2 * n_civ, region->ref_iv, n_riv * 8, hipMemcpyHostToDevice, s));
-            tv.civ = d;
-            tv.n_civ = (uint32_t)n_civ;
-            tv.riv = d + 2 * n_civ;
-            tv.n_riv = (uint32_t)n_riv;
-        }
-        TravGraph G{};
-        G.n_nodes = nn;
-        G.n_pos = np;
-        G.n_edges = ne;
-        G.ncode = (uint32_t *)d_ncode;
-        G.npos_off = (uint32_t *)d_npos;
-        G.nedge_off = (uint32_t *)d_nedge;
-        G.vpos = (uint64_t *)d_vpos;
-        G.vcnt = (uint16_t *)d_vcnt;
-        G.vnode = (uint32_t *)d_vnode;
-        G.eto = (uint32_t *)d_eto;
-        G.estep = (uint32_t *)d_estep;
-        G.bitmap = (uint64_t *)d_bitmap;
-        G.rank = (uint32_t *)d_rank;
-        uint64_t c[3] = {nn, np, ne};
-        const int r = trav_compact((const uint32_t *)d_tkey, (const uint64_t *)d_tval, (const uint32_t *)d_tseg, (const uint16_t *)d_tcnt, T, (const uint32_t *)d_ekey,
-                                   (const uint64_t *)d_eval, (const uint32_t *)d_eseg, E, k, nn, np, ne, G, d_tmp, tmp_bytes, s, region ? &tv : nullptr, c);
-        if (r != PAG_OK) return r;
-        PAG_HIP_TRY(hipStreamSynchronize(s));
-        if (c[0] > nn || c[1] > np || c[2] > ne) {
-            set_error("pag_debug_trav_compact: the view holds more than the caller's counts");
-            return PAG_EFAULT;
-        }
-        if (c[1]) {
-            PAG_HIP_TRY(hipMemcpyAsync(vpos, d_vpos, c[1] * 8, hipMemcpyDeviceToHost, s));
-            PAG_HIP_TRY(hipMemcpyAsync(vcnt, d_vcnt, c[1] * 2, hipMemcpyDeviceToHost, s));
-            PAG_HIP_TRY(hipMemcpyAsync(vnode, d_vnode, c[1] * 4, hipMemcpyDeviceToHost, s));
-        }
-        if (c[0]) PAG_HIP_TRY(hipMemcpyAsync(ncode, d_ncode, c[0] * 4, hipMemcpyDeviceToHost, s));
-        PAG_HIP_TRY(hipMemcpyAsync(npos_off, d_npos, (c[0] + 1) * 4, hipMemcpyDeviceToHost, s));
-        PAG_HIP_TRY(hipMemcpyAsync(nedge_off, d_nedge, (c[0] + 1) * 4, hipMemcpyDeviceToHost, s));
-        if (c[2]) {
-            PAG_HIP_TRY(hipMemcpyAsync(eto, d_eto, c[2] * 4, hipMemcpyDeviceToHost, s));
-            PAG_HIP_TRY(hipMemcpyAsync(estep, d_estep, c[2] * 4, hipMemcpyDeviceToHost, s));
-        }
-        PAG_HIP_TRY(hipStreamSynchronize(s));
-        counts[0] = c[0];
-        counts[1] = c[1];
-        counts[2] = c[2];
-        return PAG_OK;
-    };
-    const int rc = run();
-    if (s) hipStreamSynchronize(s);
-    for (void *p : {d_tkey, d_tval, d_tseg, d_tcnt, d_ekey, d_eval, d_eseg, d_iv, d_vpos, d_vcnt, d_vnode, d_ncode, d_npos, d_nedge, d_eto, d_estep, d_bitmap, d_rank, d_tmp})
-        if (p) hipFree(p);
-    if (s) hipStreamDestroy(s);
-    hipSetDevice(before);
-    return rc;
+    DevCall D("pag_debug_trav_compact");
+    uint32_t *d_tkey, *d_tseg, *d_ekey, *d_eseg, *d_iv;
+    uint64_t *d_tval, *d_eval;
+    uint16_t *d_tcnt;
+    char *d_tmp;
+    TravGraph G{};
+    G.n_nodes = nn;
+    G.n_pos = np;
+    G.n_edges = ne;
+    // (the sizes trav_prepare_graph gives the arrays of the traversal graph; the node arrays with room for a node per vertex:
+    // a slot wrongly taken for the first of its segment is then reported by the comparison, not written astray)
+    const uint64_t nn_room = std::max(nn, np);
+    int rc;
+    if ((rc = D.open(device, true, hipStreamDefault)) || (rc = D.up(tkey, T, &d_tkey, 16)) || (rc = D.up(tval, T, &d_tval, 16)) || (rc = D.up(tseg, T, &d_tseg, 16)) ||
+        (rc = D.up(tcnt, T, &d_tcnt, 16)) || (rc = D.up(ekey, E, &d_ekey, 16)) || (rc = D.up(eval, E, &d_eval, 16)) || (rc = D.up(eseg, E, &d_eseg, 16)) ||
+        (rc = D.alloc(&d_iv, 2 * (n_civ + n_riv + 4))) || (rc = D.alloc(&G.ncode, nn_room + 1)) || (rc = D.alloc(&G.npos_off, nn_room + 2)) ||
+        (rc = D.alloc(&G.nedge_off, nn_room + 2)) || (rc = D.alloc(&G.vpos, np + 4)) || (rc = D.alloc(&G.vcnt, np + 1)) || (rc = D.alloc(&G.vnode, np + 1)) ||
+        (rc = D.alloc(&G.eto, ne + 4)) || (rc = D.alloc(&G.estep, ne + 4)) || (rc = D.alloc(&G.bitmap, n_words)) || (rc = D.alloc(&G.rank, n_words)) ||
+        (rc = D.alloc(&d_tmp, tmp_bytes)))
+        return rc;
+    const hipStream_t s = D.s;
+    PAG_HIP_TRY(hipMemsetAsync(G.npos_off, 0, (nn + 2) * 4, s));
+    TravView tv{};
+    if (region) {
+        if (n_civ) PAG_HIP_TRY(hipMemcpyAsync(d_iv, region->ctg_iv, n_civ * 8, hipMemcpyHostToDevice, s));
+        if (n_riv) PAG_HIP_TRY(hipMemcpyAsync(d_iv + 2 * n_civ, region->ref_iv, n_riv * 8, hipMemcpyHostToDevice, s));
+        tv.civ = d_iv;
+        tv.n_civ = (uint32_t)n_civ;
+        tv.riv = d_iv + 2 * n_civ;
+        tv.n_riv = (uint32_t)n_riv;
+    }
+    uint64_t c[3] = {nn, np, ne};
+    if ((rc = trav_compact(d_tkey, d_tval, d_tseg, d_tcnt, T, d_ekey, d_eval, d_eseg, E, k, nn, np, ne, G, d_tmp, tmp_bytes, s, region ? &tv : nullptr, c))) return rc;
+    PAG_HIP_TRY(hipStreamSynchronize(s));
+    if (c[0] > nn || c[1] > np || c[2] > ne) {
+        set_error("pag_debug_trav_compact: the view holds more than the caller's counts");
+        return PAG_EFAULT;
+    }
+    if ((rc = D.down(vpos, G.vpos, c[1])) || (rc = D.down(vcnt, G.vcnt, c[1])) || (rc = D.down(vnode, G.vnode, c[1])) || (rc = D.down(ncode, G.ncode, c[0])) ||
+        (rc = D.down(npos_off, G.npos_off, c[0] + 1)) || (rc = D.down(nedge_off, G.nedge_off, c[0] + 1)) || (rc = D.down(eto, G.eto, c[2])) ||
+        (rc = D.down(estep, G.estep, c[2])) || (rc = D.finish()))
+        return rc;
+    counts[0] = c[0];
+    counts[1] = c[1];
+    counts[2] = c[2];
+    return PAG_OK;
 }
 
 // k_ctg_nodes on caller-given HOST arrays (trav_hook.hpp).  The device copy of `packed` is as long as setup_contigs makes it:
@@ -793,10 +720,10 @@ extern "C" int pag_debug_ctg_nodes(const pag_debug_trav_graph *g, const uint8_t 
         if (n_kmers && (byte_off > packed_bytes || 4 * (((len - k) >> 4) + 2) > packed_bytes - byte_off)) return PAG_EINVAL;
         cj[j] = TravCtgNodesJob{byte_off, out_off, (uint32_t)len, jobs[4 * j + 3] ? 1 : 0};
     }
-    HookDev D;
+    DevCall D("test hook");
     TravGraph G;
     int rc;
-    if ((rc = D.open(device)) || (rc = hook_upload_graph(D, g, &G))) return rc;
+    if ((rc = D.open(device, true, hipStreamDefault)) || (rc = hook_upload_graph(D, g, &G))) return rc;
     uint8_t *d_packed = nullptr;
     uint32_t *d_out = nullptr;
     TravCtgNodesJob *d_jobs = nullptr;

@@ -467,10 +467,10 @@ int hook_contigs(const pag_debug_trav_contig *ctgs, uint32_t n_ctgs, uint64_t n_
 extern "C" int pag_debug_trav_bounds(const pag_debug_trav_graph *g, const uint32_t *coords, uint32_t n, uint32_t *out, pag_debug_trav_contig *ctgs,
                                      uint32_t n_ctgs, int device) {
     if (!g || (g->n_pos && !g->upos) || (n && (!coords || !out)) || (n_ctgs && !ctgs)) return PAG_EINVAL;
-    HookDev D;
+    DevCall D("test hook");
     TravGraph G;
     int rc;
-    if ((rc = D.open(device)) || (rc = hook_upload_graph(D, g, &G))) return rc;
+    if ((rc = D.open(device, true, hipStreamDefault)) || (rc = hook_upload_graph(D, g, &G))) return rc;
     uint32_t *d_coords = nullptr, *d_out = nullptr;
     TravContig *d_tc = nullptr;
     std::vector<TravContig> tc(n_ctgs, TravContig{});
@@ -512,10 +512,10 @@ extern "C" int pag_debug_trav_seeds(const pag_debug_trav_graph *g, int which, co
         rq[r].right = reqs[4 * r + 2];
         rq[r].pos = reqs[4 * r + 3];
     }
-    HookDev D;
+    DevCall D("test hook");
     TravGraph G;
     int rc;
-    if ((rc = D.open(device)) || (rc = hook_upload_graph(D, g, &G))) return rc;
+    if ((rc = D.open(device, true, hipStreamDefault)) || (rc = hook_upload_graph(D, g, &G))) return rc;
     uint32_t *d_nodes = nullptr, *d_gbits = nullptr, *d_gset = nullptr, *d_out = nullptr;
     TravContig *d_tc = nullptr;
     TravSeedReq *d_rq = nullptr;
@@ -543,10 +543,10 @@ extern "C" int pag_debug_pack_paths(const pag_debug_trav_graph *g, const uint32_
         if (from > n_seq || len > n_seq - from || len > max_len || (leap && !seq_x)) return PAG_EINVAL;
         if (off > out_words || trav_pack_words(len, leap) > out_words - off) return PAG_EINVAL;
     }
-    HookDev D;
+    DevCall D("test hook");
     TravGraph G;
     int rc;
-    if ((rc = D.open(device)) || (rc = hook_upload_graph(D, g, &G))) return rc;
+    if ((rc = D.open(device, true, hipStreamDefault)) || (rc = hook_upload_graph(D, g, &G))) return rc;
     uint32_t *d_v = nullptr, *d_s = nullptr, *d_out = nullptr;
     uint64_t *d_x = nullptr;
     TravPackDesc *d_desc = nullptr;
@@ -581,9 +581,9 @@ extern "C" int pag_debug_commit(const uint32_t *seq_v, uint64_t len, uint32_t in
         for (uint32_t x = 0; x < ncap; ++x) empty += gset[x] == HS_EMPTY;
         if (empty <= distinct) return PAG_EINVAL;
     }
-    HookDev D;
+    DevCall D("test hook");
     int rc;
-    if ((rc = D.open(device))) return rc;
+    if ((rc = D.open(device, true, hipStreamDefault))) return rc;
     uint32_t *d_v = nullptr, *d_bits = nullptr, *d_set = nullptr;
     if ((rc = D.up(seq_v, len, &d_v)) || (rc = D.up((const uint32_t *)gbits, n_gbits, &d_bits)) || (rc = D.up((const uint32_t *)gset, (uint64_t)ncap, &d_set))) return rc;
     trav_launch_commit(d_v, len, in_lo, in_hi, d_bits + gbits_off, d_set, ncap - 1, D.s);
@@ -595,9 +595,9 @@ extern "C" int pag_debug_clear_ranges(uint8_t *buf, uint64_t bytes, const uint64
     if ((bytes && !buf) || (n && !ranges)) return PAG_EINVAL;
     for (uint64_t i = 0; i < n; ++i)
         if (ranges[3 * i] > bytes || ranges[3 * i + 1] > bytes - ranges[3 * i] || ranges[3 * i + 2] > 0xFFFFFFFFull) return PAG_EINVAL;
-    HookDev D;
+    DevCall D("test hook");
     int rc;
-    if ((rc = D.open(device))) return rc;
+    if ((rc = D.open(device, true, hipStreamDefault))) return rc;
     uint8_t *d_buf = nullptr;
     TravClear *d_r = nullptr;
     if ((rc = D.up((const uint8_t *)buf, bytes, &d_buf, 256))) return rc;
@@ -620,9 +620,9 @@ extern "C" int pag_debug_concat_parts(const uint32_t *src_v, const uint32_t *src
         const uint64_t from = parts[3 * i], start = parts[3 * i + 1], m = parts[3 * i + 2];
         if (from > n_src || m > n_src - from || start > n_out || m > n_out - start) return PAG_EINVAL;
     }
-    HookDev D;
+    DevCall D("test hook");
     int rc;
-    if ((rc = D.open(device))) return rc;
+    if ((rc = D.open(device, true, hipStreamDefault))) return rc;
     uint32_t *d_sv = nullptr, *d_ss = nullptr, *d_ov = nullptr, *d_os = nullptr;
     TravConcatPart *d_p = nullptr;
     if ((rc = D.up(src_v, n_src, &d_sv)) || (rc = D.up(src_s, n_src, &d_ss)) || (rc = D.up((const uint32_t *)out_v, n_out, &d_ov)) ||
@@ -642,10 +642,10 @@ extern "C" int pag_debug_gathers(const pag_debug_trav_graph *g, int which, const
     if (which == 0 ? !g->upos : (!g->vpos || !g->vcnt || !g->vnode || !g->ncode || (which == 1 && !g->uold))) return PAG_EINVAL;
     for (uint64_t i = 0; i < len; ++i)
         if (seq_v[i] >= g->n_pos) return PAG_EINVAL;
-    HookDev D;
+    DevCall D("test hook");
     TravGraph G;
     int rc;
-    if ((rc = D.open(device)) || (rc = hook_upload_graph(D, g, &G))) return rc;
+    if ((rc = D.open(device, true, hipStreamDefault)) || (rc = hook_upload_graph(D, g, &G))) return rc;
     uint32_t *d_v = nullptr, *d_s = nullptr;
     if ((rc = D.up(seq_v, len, &d_v)) || (rc = D.up(seq_s, seq_s ? len : 0, &d_s))) return rc;
     if (which == 0) {

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "cns_device.hpp"
+#include "dev_call.hpp"
 
 namespace pagdev {
 
@@ -29,27 +30,6 @@ __global__ __launch_bounds__(64) void cns_parts_kernel(pagcns::Arrays A, const p
 }
 
 namespace {
-struct Dev {  // device allocations of one call, freed on every way out
-    const char *who;
-    std::vector<void *> ptrs;
-    explicit Dev(const char *w) : who(w) {}
-    ~Dev() {
-        for (void *p : ptrs) (void)hipFree(p);
-    }
-    template <typename T>
-    int alloc(T **out, size_t n) {
-        void *p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) {
-            (void)hipGetLastError();
-            set_error("%s: out of device memory (%zu bytes)", who, n * sizeof(T));
-            return PAG_ENOMEM;
-        }
-        ptrs.push_back(p);
-        *out = (T *)p;
-        return PAG_OK;
-    }
-};
-
 void launch_lane(const pagcns::Arrays &A, const pagcns::Part *parts, uint32_t n, const char *backbone, const pagcns::Aln *alns, const char *qpool, const char *tpool,
                  int min_weight, char *out, uint32_t *out_len, int32_t *part_err) {
     cns_parts_kernel<<<dim3(n), dim3(64), 0, 0>>>(A, parts, n, backbone, alns, qpool, tpool, min_weight, out, out_len, part_err);
@@ -71,7 +51,7 @@ int cns_consensus_batched(const char *who, CnsLaunchFn launch, int device, const
     }
     PAG_HIP_TRY(hipSetDevice(device));
     // inputs
-    Dev D(who);
+    DevCall D(who);
     char *d_bb, *d_out;
     const char *d_q = d_qpool, *d_t = d_tpool;
     pagcns::Aln *d_alns;
@@ -137,7 +117,7 @@ int cns_consensus_batched(const char *who, CnsLaunchFn launch, int device, const
             na += s.aux_cap;
             ++p1;
         }
-        Dev B(who);
+        DevCall B(who);
         pagcns::Arrays A{};
         pagcns::Part *d_parts;
         uint32_t *d_len;

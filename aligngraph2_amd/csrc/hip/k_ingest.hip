@@ -20,6 +20,7 @@
 #include <thread>
 #include <vector>
 
+#include "dev_call.hpp"
 #include "pag_device.hpp"
 
 namespace pagdev {
@@ -116,10 +117,11 @@ __global__ void classify_kernel(const unsigned char *__restrict__ text, const ui
     }
 }
 
-// text in host memory -> a device buffer, through two pinned staging chunks filled by a few threads
-int upload_text(const char *text, uint64_t bytes, unsigned char **dev, hipStream_t s) {
-    *dev = nullptr;
-    PAG_HIP_TRY(hipMalloc((void **)dev, bytes + 64));
+// text in host memory -> a device buffer of the call's, through two pinned staging chunks filled by a few threads
+int upload_text(DevCall &D, const char *text, uint64_t bytes, unsigned char **dev) {
+    const hipStream_t s = D.s;
+    const int rc0 = D.alloc(dev, bytes, 64);
+    if (rc0) return rc0;
     PAG_HIP_TRY(hipMemsetAsync(*dev + bytes, 0, 64, s));
     const size_t CH = 64u << 20;
     char *pin[2] = {nullptr, nullptr};
@@ -132,9 +134,7 @@ int upload_text(const char *text, uint64_t bytes, unsigned char **dev, hipStream
     };
     for (int b = 0; b < 2; ++b) {
         if (hipHostMalloc((void **)&pin[b], CH, hipHostMallocDefault) != hipSuccess || hipEventCreateWithFlags(&done[b], hipEventDisableTiming) != hipSuccess) {
-            drop();  // (what the first turn of this loop took, and the device buffer: the caller sees no half-made upload)
-            hipFree(*dev);
-            *dev = nullptr;
+            drop();  // (what the first turn of this loop took)
             set_error("ingest: pinned staging buffers");
             return PAG_ENOMEM;
         }
@@ -160,22 +160,6 @@ int upload_text(const char *text, uint64_t bytes, unsigned char **dev, hipStream
     return rc;
 }
 
-struct DevTmp {  // small device arrays of one call
-    std::vector<void *> p;
-    ~DevTmp() {
-        for (void *q : p) hipFree(q);
-    }
-    template <typename T>
-    int put(const T *host, uint64_t n, T **out, hipStream_t s) {
-        void *d = nullptr;
-        PAG_HIP_TRY(hipMalloc(&d, std::max<uint64_t>(n, 1) * sizeof(T)));
-        p.push_back(d);
-        if (n) PAG_HIP_TRY(hipMemcpyAsync(d, host, n * sizeof(T), hipMemcpyHostToDevice, s));
-        *out = (T *)d;
-        return PAG_OK;
-    }
-};
-
 }  // namespace
 }  // namespace pagdev
 
@@ -199,31 +183,20 @@ int pag_pack_text_seqs(const char *text, int text_on_device, uint64_t text_bytes
         max_len = std::max(max_len, seq_len[i]);
     }
     if (n_seqs == 0) return PAG_OK;
-    hipStream_t s = nullptr;
-    unsigned char *dtext = (unsigned char *)text, *own = nullptr;
-    if (!text_on_device) {
-        if ((rc = upload_text(text, text_bytes, &own, s))) {
-            if (own) hipFree(own);
-            return rc;
-        }
-        dtext = own;
+    DevCall t("pag_pack_text_seqs");  // (on the null stream)
+    unsigned char *dtext = (unsigned char *)text;
+    if (!text_on_device && (rc = upload_text(t, text, text_bytes, &dtext))) return rc;
+    uint64_t *d_so, *d_bo;
+    uint32_t *d_sl;
+    if ((rc = t.up(seq_off, n_seqs, &d_so, 0)) || (rc = t.up(seq_len, n_seqs, &d_sl, 0)) || (rc = t.up(byte_off, n_seqs, &d_bo, 0))) return rc;
+    const uint32_t words = (max_len + 15u) / 16u;
+    const unsigned parts = std::max(1u, std::min(1024u, (words + 4095u) / 4096u));
+    // (2^31 - 1 blocks in x: more sequences than that would be more than the 2^32-coordinate space holds)
+    pack_text_kernel<<<dim3((unsigned)n_seqs, parts), dim3(256), 0, t.s>>>(dtext, d_so, d_sl, d_bo, packed_dev);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(t.s) != hipSuccess) {
+        set_error("pag_pack_text_seqs: kernel failed");
+        rc = PAG_EFAULT;
     }
-    {
-        DevTmp t;
-        uint64_t *d_so, *d_bo;
-        uint32_t *d_sl;
-        if (!(rc = t.put(seq_off, n_seqs, &d_so, s)) && !(rc = t.put(seq_len, n_seqs, &d_sl, s)) && !(rc = t.put(byte_off, n_seqs, &d_bo, s))) {
-            const uint32_t words = (max_len + 15u) / 16u;
-            const unsigned parts = std::max(1u, std::min(1024u, (words + 4095u) / 4096u));
-            // (2^31 - 1 blocks in x: more sequences than that would be more than the 2^32-coordinate space holds)
-            pack_text_kernel<<<dim3((unsigned)n_seqs, parts), dim3(256), 0, s>>>(dtext, d_so, d_sl, d_bo, packed_dev);
-            if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-                set_error("pag_pack_text_seqs: kernel failed");
-                rc = PAG_EFAULT;
-            }
-        }
-    }
-    if (own) hipFree(own);
     return rc;
 }
 
@@ -240,57 +213,42 @@ int pag_classify_columns(const char *text, int text_on_device, uint64_t text_byt
             return PAG_EINVAL;
         }
     if (n_recs == 0) return PAG_OK;
-    hipStream_t s = nullptr;
-    unsigned char *dtext = (unsigned char *)text, *own = nullptr;
-    if (!text_on_device) {
-        if ((rc = upload_text(text, text_bytes, &own, s))) {
-            if (own) hipFree(own);
-            return rc;
-        }
-        dtext = own;
+    DevCall t("pag_classify_columns");  // (on the null stream)
+    const hipStream_t s = t.s;
+    unsigned char *dtext = (unsigned char *)text;
+    if (!text_on_device && (rc = upload_text(t, text, text_bytes, &dtext))) return rc;
+    uint64_t *d_qo, *d_ro, *d_do;
+    uint32_t *d_ql, *d_rl;
+    if ((rc = t.up(q_off, n_recs, &d_qo, 0)) || (rc = t.up(q_len, n_recs, &d_ql, 0)) || (rc = t.up(r_off, n_recs, &d_ro, 0)) ||
+        (rc = t.up(r_len, n_recs, &d_rl, 0)) || (rc = t.up(diff_off, n_recs, &d_do, 0)))
+        return rc;
+    if (hipMemsetAsync(n_emit_dev, 0, n_recs * 4, s) != hipSuccess || hipMemsetAsync(n_radv_dev, 0, n_recs * 4, s) != hipSuccess) rc = PAG_EFAULT;
+    classify_kernel<<<dim3((unsigned)n_recs), dim3(256), 0, s>>>(dtext, d_qo, d_ql, d_ro, d_rl, d_do, diff_dev, n_emit_dev, n_radv_dev);
+    if (rc || hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+        set_error("pag_classify_columns: kernel failed");
+        rc = PAG_EFAULT;
     }
-    {
-        DevTmp t;
-        uint64_t *d_qo, *d_ro, *d_do;
-        uint32_t *d_ql, *d_rl;
-        if (!(rc = t.put(q_off, n_recs, &d_qo, s)) && !(rc = t.put(q_len, n_recs, &d_ql, s)) && !(rc = t.put(r_off, n_recs, &d_ro, s)) &&
-            !(rc = t.put(r_len, n_recs, &d_rl, s)) && !(rc = t.put(diff_off, n_recs, &d_do, s))) {
-            if (hipMemsetAsync(n_emit_dev, 0, n_recs * 4, s) != hipSuccess || hipMemsetAsync(n_radv_dev, 0, n_recs * 4, s) != hipSuccess) rc = PAG_EFAULT;
-            classify_kernel<<<dim3((unsigned)n_recs), dim3(256), 0, s>>>(dtext, d_qo, d_ql, d_ro, d_rl, d_do, diff_dev, n_emit_dev, n_radv_dev);
-            if (rc || hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-                set_error("pag_classify_columns: kernel failed");
-                rc = PAG_EFAULT;
-            }
-        }
-    }
-    if (own) hipFree(own);
     return rc;
 }
 
 // ... with the results in HOST arrays (the class words and the two counts come back in one copy each): what a host parser
-// that keeps its database in host memory calls (aln_db.cpp under PAGRAPH_DEVICE_INGEST=1)
+// that keeps its database in host memory calls (aln_db.cpp)
 int pag_classify_columns_host(const char *text, uint64_t text_bytes, const uint64_t *q_off, const uint32_t *q_len, const uint64_t *r_off,
                               const uint32_t *r_len, const uint64_t *diff_off, uint64_t n_recs, uint32_t *diff_host, uint64_t n_diff_words,
                               uint32_t *n_emit_host, uint32_t *n_radv_host, int device) {
     if (!diff_host || !n_emit_host || !n_radv_host) return PAG_EINVAL;
     if (!pag_device_available()) return PAG_ENODEV;
-    PAG_HIP_TRY(hipSetDevice(device));
+    DevCall D("pag_classify_columns_host");  // (on the null stream; the device stays current)
     uint32_t *d_diff = nullptr, *d_cnt = nullptr;
-    PAG_HIP_TRY(hipMalloc((void **)&d_diff, (n_diff_words + 4) * 4));
-    if (hipMalloc((void **)&d_cnt, (2 * n_recs + 2) * 4) != hipSuccess) {
-        hipFree(d_diff);
-        set_error("pag_classify_columns_host: out of device memory");
-        return PAG_ENOMEM;
-    }
-    int rc = pag_classify_columns(text, 0, text_bytes, q_off, q_len, r_off, r_len, diff_off, n_recs, d_diff, n_diff_words, d_cnt, d_cnt + n_recs, device);
+    int rc = D.open(device, false, DevCall::NO_STREAM);
+    if (rc || (rc = D.alloc(&d_diff, n_diff_words + 4)) || (rc = D.alloc(&d_cnt, 2 * n_recs + 2))) return rc;
+    rc = pag_classify_columns(text, 0, text_bytes, q_off, q_len, r_off, r_len, diff_off, n_recs, d_diff, n_diff_words, d_cnt, d_cnt + n_recs, device);
     if (rc == PAG_OK && (hipMemcpy(diff_host, d_diff, n_diff_words * 4, hipMemcpyDeviceToHost) != hipSuccess ||
                          hipMemcpy(n_emit_host, d_cnt, n_recs * 4, hipMemcpyDeviceToHost) != hipSuccess ||
                          hipMemcpy(n_radv_host, d_cnt + n_recs, n_recs * 4, hipMemcpyDeviceToHost) != hipSuccess)) {
         set_error("pag_classify_columns_host: copy back failed");
         rc = PAG_EFAULT;
     }
-    hipFree(d_diff);
-    hipFree(d_cnt);
     return rc;
 }
 

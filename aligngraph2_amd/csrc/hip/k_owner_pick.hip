@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <initializer_list>
 
+#include "dev_call.hpp"
 #include "pag_device.hpp"
 #include "pagraph_debug.h"
 
@@ -173,36 +174,16 @@ extern "C" int pag_debug_owner_pick(const uint32_t *key, const uint64_t *val, ui
                                     uint32_t *out_key, uint64_t *out_val, uint64_t cap, uint64_t at1, uint64_t at2, uint64_t *counts,
                                     int device) {
     if (!counts || (n && (!key || !val)) || (cap && (!out_key || !out_val))) return PAG_EINVAL;
-    int before = 0;
-    PAG_HIP_TRY(hipGetDevice(&before));
-    PAG_HIP_TRY(hipSetDevice(device));
-    void *d_key = nullptr, *d_val = nullptr, *d_ok = nullptr, *d_ov = nullptr, *d_tmp = nullptr;
-    hipStream_t s = nullptr;
-    int rc = PAG_OK;
-    auto run = [&]() -> int {
-        PAG_HIP_TRY(hipStreamCreate(&s));
-        PAG_HIP_TRY(hipMalloc(&d_key, n * 4 + 16));
-        PAG_HIP_TRY(hipMalloc(&d_val, n * 8 + 16));
-        PAG_HIP_TRY(hipMalloc(&d_ok, cap * 4 + 16));
-        PAG_HIP_TRY(hipMalloc(&d_ov, cap * 8 + 16));
-        PAG_HIP_TRY(hipMalloc(&d_tmp, owner_pick_tmp_bytes(n)));
-        if (n) PAG_HIP_TRY(hipMemcpyAsync(d_key, key, n * 4, hipMemcpyHostToDevice, s));
-        if (n) PAG_HIP_TRY(hipMemcpyAsync(d_val, val, n * 8, hipMemcpyHostToDevice, s));
-        if (cap) PAG_HIP_TRY(hipMemcpyAsync(d_ok, out_key, cap * 4, hipMemcpyHostToDevice, s));
-        if (cap) PAG_HIP_TRY(hipMemcpyAsync(d_ov, out_val, cap * 8, hipMemcpyHostToDevice, s));
-        int r = owner_pick((const uint32_t *)d_key, (const uint64_t *)d_val, n, n1, shift, owner, (uint32_t *)d_ok, (uint64_t *)d_ov, cap, at1, at2,
-                           counts, d_tmp, s);
-        if (r != PAG_OK) return r;
-        if (cap) PAG_HIP_TRY(hipMemcpyAsync(out_key, d_ok, cap * 4, hipMemcpyDeviceToHost, s));
-        if (cap) PAG_HIP_TRY(hipMemcpyAsync(out_val, d_ov, cap * 8, hipMemcpyDeviceToHost, s));
-        PAG_HIP_TRY(hipStreamSynchronize(s));
-        return PAG_OK;
-    };
-    rc = run();
-    if (s) hipStreamSynchronize(s);
-    for (void *p : {d_key, d_val, d_ok, d_ov, d_tmp})
-        if (p) hipFree(p);
-    if (s) hipStreamDestroy(s);
-    hipSetDevice(before);
-    return rc;
+    DevCall D("pag_debug_owner_pick");
+    uint32_t *d_key = nullptr, *d_ok = nullptr;
+    uint64_t *d_val = nullptr, *d_ov = nullptr;
+    char *d_tmp = nullptr;
+    int rc;
+    if ((rc = D.open(device, true, hipStreamDefault)) || (rc = D.up(key, n, &d_key, 16)) || (rc = D.up(val, n, &d_val, 16)) || (rc = D.up((const uint32_t *)out_key, cap, &d_ok, 16)) ||
+        (rc = D.up((const uint64_t *)out_val, cap, &d_ov, 16)) || (rc = D.alloc(&d_tmp, owner_pick_tmp_bytes(n))))
+        return rc;
+    if ((rc = owner_pick(d_key, d_val, n, n1, shift, owner, d_ok, d_ov, cap, at1, at2, counts, d_tmp, D.s)) || (rc = D.down(out_key, d_ok, cap)) ||
+        (rc = D.down(out_val, d_ov, cap)))
+        return rc;
+    return D.finish();
 }

@@ -184,9 +184,7 @@ extern "C" int pag_shard_release_build(pag_graph *g) {
     for (int i = 0; i < ps::COUNT; ++i) {
         pag_graph::Slot &sl = g->pool[i];
         if (!ps::released_after_import((ps::Id)i) || !sl.p || std::find(held.p, held.p + ps::GRAPH_ARRS, sl.p) != held.p + ps::GRAPH_ARRS) continue;
-        hipFree(sl.p);
-        sl.p = nullptr;
-        sl.cap = 0;
+        slot_free(g, sl);
     }
     return PAG_OK;
 }

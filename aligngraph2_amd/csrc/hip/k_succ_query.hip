@@ -25,6 +25,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "dev_call.hpp"
 #include "pag_graph_impl.hpp"
 #include "trav_device.hpp"
 
@@ -194,12 +195,12 @@ struct BatchLayout {
     }
 };
 
-struct BatchScratch {  // freed when the call returns, whichever way
-    void *a = nullptr, *b = nullptr;
+struct BatchScratch : DevCall {  // on the handle's stream; the events of the two timings
+    char *a = nullptr;
+    SuccOut *b = nullptr;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    BatchScratch() : DevCall("pag_successors_batch") {}
     ~BatchScratch() {
-        if (a) hipFree(a);
-        if (b) hipFree(b);
         for (hipEvent_t e : ev)
             if (e) hipEventDestroy(e);
     }
@@ -234,29 +235,23 @@ int pag_successors_batch(const pag_graph *g, const pag_succ_query *q, uint64_t n
     }
     off[0] = 0;
     if (n_q == 0) return PAG_OK;
-    PAG_HIP_TRY(hipSetDevice(g->device));
-    hipStream_t s = g->stream;
     BatchScratch B;
+    const hipStream_t s = B.s = g->stream;
     const BatchLayout L(n_q);
-    hipError_t e = hipMalloc(&B.a, L.bytes);
-    if (e != hipSuccess) {
-        B.a = nullptr;
-        set_error("pag_successors_batch: hipMalloc(%zu) failed: %s", L.bytes, hipGetErrorString(e));
-        return PAG_ENOMEM;
-    }
+    int rc = B.open(g->device, false, DevCall::NO_STREAM);
+    if (rc || (rc = B.alloc(&B.a, L.bytes))) return rc;
     for (hipEvent_t &ev : B.ev) PAG_HIP_TRY(hipEventCreate(&ev));
-    pag_succ_query *d_q = (pag_succ_query *)((char *)B.a + L.q);
-    uint64_t *d_off = (uint64_t *)((char *)B.a + L.off);
-    uint32_t *d_cnt = (uint32_t *)((char *)B.a + L.cnt);
-    int32_t *d_status = (int32_t *)((char *)B.a + L.status);
+    pag_succ_query *d_q = (pag_succ_query *)(B.a + L.q);
+    uint64_t *d_off = (uint64_t *)(B.a + L.off);
+    uint32_t *d_cnt = (uint32_t *)(B.a + L.cnt);
+    int32_t *d_status = (int32_t *)(B.a + L.status);
     QueryGraph G{g->tkey, g->tval, g->tseg, g->ekey, g->eval, g->eseg, g->n_t, g->n_e};
     const uint32_t dev = (uint32_t)std::min<uint64_t>(deviation, 0xFFFFFFFFull);  // (coordinates are 32 bits: so is every difference of two)
     PAG_HIP_TRY(hipMemcpyAsync(d_q, q, n_q * sizeof(pag_succ_query), hipMemcpyHostToDevice, s));
     PAG_HIP_TRY(hipEventRecord(B.ev[0], s));
     k_succ_query<false><<<dim3(query_grid(n_q)), dim3(256), 0, s>>>(G, d_q, n_q, dev, error_rate, d_cnt, d_status, nullptr, nullptr, 0);
     PAG_HIP_TRY(hipGetLastError());
-    int rc = scan_u32_to_u64(d_cnt, d_off, n_q, d_off + n_q, (char *)B.a + L.scan, s);
-    if (rc != PAG_OK) return rc;
+    if ((rc = scan_u32_to_u64(d_cnt, d_off, n_q, d_off + n_q, B.a + L.scan, s))) return rc;
     PAG_HIP_TRY(hipEventRecord(B.ev[1], s));
     PAG_HIP_TRY(hipMemcpyAsync(off, d_off, (n_q + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     if (status) PAG_HIP_TRY(hipMemcpyAsync(status, d_status, n_q * sizeof(int32_t), hipMemcpyDeviceToHost, s));
@@ -271,14 +266,9 @@ int pag_successors_batch(const pag_graph *g, const pag_succ_query *q, uint64_t n
         return PAG_ERANGE;
     }
     if (total == 0) return PAG_OK;
-    e = hipMalloc(&B.b, total * sizeof(pag_succ));
-    if (e != hipSuccess) {
-        B.b = nullptr;
-        set_error("pag_successors_batch: hipMalloc(%llu) failed: %s", (unsigned long long)(total * sizeof(pag_succ)), hipGetErrorString(e));
-        return PAG_ENOMEM;
-    }
+    if ((rc = B.alloc(&B.b, total))) return rc;
     PAG_HIP_TRY(hipEventRecord(B.ev[2], s));
-    k_succ_query<true><<<dim3(query_grid(n_q)), dim3(256), 0, s>>>(G, d_q, n_q, dev, error_rate, nullptr, nullptr, d_off, (SuccOut *)B.b, total);
+    k_succ_query<true><<<dim3(query_grid(n_q)), dim3(256), 0, s>>>(G, d_q, n_q, dev, error_rate, nullptr, nullptr, d_off, B.b, total);
     PAG_HIP_TRY(hipGetLastError());
     PAG_HIP_TRY(hipEventRecord(B.ev[3], s));
     PAG_HIP_TRY(hipMemcpyAsync(out, B.b, total * sizeof(pag_succ), hipMemcpyDeviceToHost, s));

@@ -249,22 +249,13 @@ void pag_destroy(pag_graph *g) {
     if (!g) return;
     hipSetDevice(g->device);
     free_graph_results(g);
-    for (auto &sl : g->pool)
-        if (sl.p) hipFree(sl.p);
-    for (auto &sl : g->cpool)
-        if (sl.p) hipFree(sl.p);
-    for (void *q : g->deferred) hipFree(q);
-    if (g->wq_host) hipHostFree(g->wq_host);
-    if (g->path_store) hipHostFree(g->path_store);
+    drain_deferred(g);
+    for (auto &sl : g->pool) slot_free(g, sl);
+    for (auto &sl : g->cpool) slot_free(g, sl);
     if (g->deliver_stream) hipStreamDestroy(g->deliver_stream);
-    if (g->pin_host) hipHostFree(g->pin_host);
-    for (void *q : g->fetch_chunks) hipHostFree(q);
+    for (OwnedBuf *b : {&g->wq_host, &g->wq_next, &g->path_store, &g->pin_host, &g->walk_arena, &g->dump_tables, &g->dump_scratch}) b->release();
+    for (OwnedBuf &c : g->fetch_chunks) c.release();
     g->fetch_chunks.clear();
-    g->fetch_chunk_bytes.clear();
-    if (g->walk_arena) hipFree(g->walk_arena);
-    if (g->dump_tables) hipFree(g->dump_tables);
-    if (g->dump_scratch) hipFree(g->dump_scratch);
-    if (g->wq_next) hipFree(g->wq_next);
     for (hipStream_t ws : g->walk_streams) hipStreamDestroy(ws);
     if (g->solid_bits) hipFree(g->solid_bits);
     if (g->stream) hipStreamDestroy(g->stream);
@@ -681,42 +672,30 @@ extern "C" int pag_reserve_walk_arena(pag_graph *g, uint64_t contig_bases) {
     // (the same cap as pag_travel's own estimate: an arena reserved here must not be thrown away there as too small)
     // (processes that share the device — PAG_DEVICE_SHARERS, the one-GPU test box — share that cap)
     const size_t sharers = env_device_sharers();
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) want = std::min(want, (free_b + g->walk_arena_cap) * 2 / 5 / sharers);
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) want = std::min(want, (free_b + g->walk_arena.cap) * 2 / 5 / sharers);
     // the pinned memory the fetched paths of the walks' jobs land in (64 MB chunks kept by the handle, pag_travel's
     // fetch_alloc): ~14 bytes per contig base at sequencing coverage; a cold process otherwise pins them one by one between
     // the walks' first fetches (5 ms each)
     {
         const size_t FETCH_CHUNK = 64u << 20;
         size_t have = 0;
-        for (size_t b : g->fetch_chunk_bytes) have += b;
+        for (const OwnedBuf &c : g->fetch_chunks) have += c.cap;
         // (PAGRAPH_DEVICE_DUMPS=1, the switch of the callers that will ask pag_travel for the dump text: its buffers come out of the
         // same chunks, ~0.24 path vertices per contig base at up to ~90 bytes of a line's bound)
         // (PAGRAPH_DEVICE_SEQS=1 likewise: a path's sequence is about as long as its contig)
         const size_t per_base = 14 + (env_int("PAGRAPH_DEVICE_DUMPS", 0) == 1 ? 22 : 0) + (env_int("PAGRAPH_DEVICE_SEQS", 0) == 1 ? 2 : 0);
         const size_t want_pinned = std::min<size_t>((size_t)contig_bases * per_base, (size_t)4 << 30);
         while (have < want_pinned) {
-            void *q = nullptr;
-            if (hipHostMalloc(&q, FETCH_CHUNK, hipHostMallocDefault) != hipSuccess) {
+            if (!fetch_chunk_add(g, FETCH_CHUNK)) {
                 (void)hipGetLastError();
                 break;  // (pag_travel asks again when it needs the memory, and reports a failure there)
             }
-            g->fetch_chunks.push_back(q);
-            g->fetch_chunk_bytes.push_back(FETCH_CHUNK);
             have += FETCH_CHUNK;
         }
     }
     // (and the streams the walker waves are launched on: ~6 ms each to create, here beside the caller's other work)
     pagdev::WalkerGrid::prepare_streams(g, 4);
-    if (g->walk_arena_cap >= want) return PAG_OK;
-    if (g->walk_arena) hipFree(g->walk_arena);
-    g->walk_arena = nullptr;
-    g->walk_arena_cap = 0;
-    if (hipMalloc(&g->walk_arena, want) != hipSuccess) {
-        g->walk_arena = nullptr;
-        (void)hipGetLastError();
-        return PAG_OK;  // (pag_travel tries again, or works without the arena)
-    }
-    g->walk_arena_cap = want;
+    if (g->walk_arena.grow(g, want, want) != hipSuccess) (void)hipGetLastError();  // (pag_travel tries again, or works without the arena)
     return PAG_OK;
 }
 
@@ -1070,6 +1049,50 @@ int pag_debug_streams(const pag_graph *g, uint32_t *tkey, uint64_t *tval, uint32
     std::memcpy(tval, g->dbg_tval.data(), g->dbg_tval.size() * 8);
     std::memcpy(ekey, g->dbg_ekey.data(), g->dbg_ekey.size() * 4);
     std::memcpy(eval, g->dbg_eval.data(), g->dbg_eval.size() * 8);
+    return PAG_OK;
+}
+// slot_grow / slot_free / drain_deferred on the scratch handle's slot ps::PICK_TMP, step by step (pagraph_debug.h)
+int pag_debug_slot_grow(pag_graph *g, const uint64_t *steps, uint32_t n_steps, uint64_t *out, uint8_t *kept, uint64_t kept_stride) {
+    if (!g || (n_steps && (!steps || !out)) || (kept_stride && !kept)) return PAG_EINVAL;
+    PAG_HIP_TRY(hipSetDevice(g->device));
+    pag_graph::Slot &sl = g->pool[ps::PICK_TMP];
+    std::vector<uint8_t> was, now;
+    for (uint32_t i = 0; i < n_steps; ++i) {
+        const uint64_t need = steps[4 * i], want = steps[4 * i + 1], keep = steps[4 * i + 2], op = steps[4 * i + 3];
+        uint64_t *o = out + 5 * (size_t)i;
+        int rc = PAG_OK;
+        o[4] = 0;
+        if (op <= 1) {
+            void *const old = sl.p;
+            g->defer_free = op == 1;
+            rc = slot_grow(g, sl, need, want, keep, g->stream);
+            g->defer_free = false;
+            if (rc == PAG_OK && keep) {
+                now.resize(keep);
+                PAG_HIP_TRY(hipMemcpy(now.data(), sl.p, keep, hipMemcpyDeviceToHost));
+                if (kept_stride) std::memcpy(kept + (size_t)i * kept_stride, now.data(), std::min<uint64_t>(keep, kept_stride));
+                if (sl.p != old && !g->deferred.empty() && g->deferred.back().p == old) {  // (parked: still there to be read)
+                    was.resize(keep);
+                    PAG_HIP_TRY(hipMemcpy(was.data(), old, keep, hipMemcpyDeviceToHost));
+                    o[4] = was == now;
+                }
+            }
+        } else if (op == 2) {
+            drain_deferred(g);
+        } else if (op == 3) {
+            now.resize(sl.cap);
+            for (size_t b = 0; b < now.size(); ++b) now[b] = (uint8_t)(b * 7 + need);
+            if (sl.cap) PAG_HIP_TRY(hipMemcpy(sl.p, now.data(), sl.cap, hipMemcpyHostToDevice));
+        } else if (op == 4) {
+            slot_free(g, sl);
+        } else {
+            rc = PAG_EINVAL;
+        }
+        o[0] = (uint64_t)(int64_t)rc;
+        o[1] = (uint64_t)(uintptr_t)sl.p;
+        o[2] = sl.cap;
+        o[3] = g->deferred.size();
+    }
     return PAG_OK;
 }
 

@@ -8,7 +8,36 @@
 #include "pag_travel.hpp"
 #include "pool_slots.hpp"
 
+namespace pagdev {
+// A buffer the handle owns outside the pool: one allocation, replaced (never copied) when it is too small.
+struct OwnedBuf {
+    enum Kind : uint8_t { DEVICE, PINNED, PINNED_MAPPED };  // hipMalloc; hipHostMalloc default; coherent + mapped
+    void *p = nullptr;
+    size_t cap = 0;
+    Kind kind = DEVICE;
+    explicit OwnedBuf(Kind k = DEVICE) : kind(k) {}
+    static void free_raw(void *q, Kind k) {
+        if (!q) return;
+        if (k == DEVICE) hipFree(q);
+        else hipHostFree(q);
+    }
+    // room for `need` bytes: a buffer that has them stays, any other is replaced by one of `want` bytes (its contents are
+    // dropped; under g->defer_free the old one is parked in g->deferred).  After a failure the buffer is empty.
+    inline hipError_t grow(pag_graph *g, size_t need, size_t want);
+    void release() {
+        free_raw(p, kind);
+        p = nullptr;
+        cap = 0;
+    }
+    template <typename T>
+    T *as() const {
+        return (T *)p;
+    }
+};
+}  // namespace pagdev
+
 struct pag_graph {
+    using OwnedBuf = pagdev::OwnedBuf;
     int device = 0;
     hipStream_t stream = nullptr;
     uint32_t k = 0;
@@ -50,14 +79,16 @@ struct pag_graph {
     uint64_t alloc_bytes = 0, alloc_calls = 0;
     // per-contig walker buffers (k5_travel_host.hip), grown on demand like the slots above
     std::vector<Slot> cpool;
-    // while the persistent walker is resident nothing may be hipFree'd (it synchronises the device): replaced
-    // buffers are parked here and released afterwards
+    // while the persistent walker is resident nothing may be freed, device or pinned memory (either synchronises the device):
+    // replaced buffers are parked here and released afterwards (drain_deferred)
     bool defer_free = false;
-    std::vector<void *> deferred;
+    struct Parked {
+        void *p;
+        OwnedBuf::Kind kind;
+    };
+    std::vector<Parked> deferred;
     // job queue of the persistent walker (fine-grained host memory) and its device-side ticket counter
-    void *wq_host = nullptr;
-    size_t wq_bytes = 0;
-    uint32_t *wq_next = nullptr;
+    OwnedBuf wq_host{OwnedBuf::PINNED_MAPPED}, wq_next;
     std::vector<hipStream_t> walk_streams;  // the walker launches' streams (WalkerGrid, walker_grid.hpp)
     // traversal state (k5_travel_host.hip)
     pagdev::TravGraph tg{};
@@ -66,8 +97,7 @@ struct pag_graph {
     double tg_err = 0;
     // result of the last pag_travel: one array in pinned host memory (grown, never released before pag_destroy), slot
     // 2 * contig + (reverse ? 1 : 0) at path_off / path_len
-    pag_path_node *path_store = nullptr;
-    size_t path_cap = 0;
+    OwnedBuf path_store{OwnedBuf::PINNED};
     std::vector<uint64_t> path_off, path_len;
     hipStream_t deliver_stream = nullptr;  // copies of finished contigs' paths while the walks run (pag_travel)
     std::vector<const pag_path_node *> path_ptr;  // non-null: the orientation's path, delivered while the walks ran (pinned fetch memory)
@@ -81,13 +111,11 @@ struct pag_graph {
     std::vector<const char *> seq_ptr;
     std::vector<uint64_t> seq_len;
     const pag_seqs *seq_refs = nullptr;
-    void *dump_tables = nullptr, *dump_scratch = nullptr;
-    size_t dump_tables_cap = 0, dump_scratch_cap = 0;
+    OwnedBuf dump_tables, dump_scratch;
     // device arena of the walker's job buffers (bump pointer, reset by every pag_travel)
-    void *walk_arena = nullptr;
-    size_t walk_arena_cap = 0, walk_arena_used = 0;
-    std::vector<void *> fetch_chunks;  // pinned chunks for the paths fetched from the walker (pag_travel)
-    std::vector<size_t> fetch_chunk_bytes;
+    OwnedBuf walk_arena;
+    size_t walk_arena_used = 0;
+    std::vector<OwnedBuf> fetch_chunks;  // pinned chunks for the paths fetched from the walker (pag_travel)
     // the graph holds only a region of the block (pag_shard_set_region after pag_shard_import): the reference bands of its
     // coordinate-free vertices, [lo, hi) pairs sorted, and which ends are open (the block goes on beyond them, on other ranks)
     bool regional = false;
@@ -103,8 +131,7 @@ struct pag_graph {
     double succ_per_vertex = 3.0;  // emission-stream slots per vertex of the last traversal graph: sizes the stream of the next (trav_prepare_graph)
     uint64_t n_zero_ctg = 0;  // new ids below it: vertices without a contig coordinate, in reference-coordinate order
     // pinned host staging area of the traversal (packed job results, uploads)
-    void *pin_host = nullptr;
-    size_t pin_bytes = 0;
+    OwnedBuf pin_host{OwnedBuf::PINNED};
     // debug: raw emitted streams (host copies), kept when PAG_DEBUG_KEEP_STREAMS=1
     std::vector<uint32_t> dbg_tkey, dbg_ekey;
     std::vector<uint64_t> dbg_tval, dbg_eval;
@@ -113,6 +140,81 @@ struct pag_graph {
 
 namespace pagdev {
 
+// what the walker's residency parked (pag_graph::deferred) is released; the caller knows the grid is down
+inline void drain_deferred(pag_graph *g) {
+    g->defer_free = false;
+    for (const pag_graph::Parked &q : g->deferred) OwnedBuf::free_raw(q.p, q.kind);
+    g->deferred.clear();
+}
+// an allocation of the handle that is no longer wanted: freed, or parked while nothing may be freed
+inline void retire(pag_graph *g, void *p, OwnedBuf::Kind kind) {
+    if (!p) return;
+    if (g->defer_free) g->deferred.push_back({p, kind});
+    else OwnedBuf::free_raw(p, kind);
+}
+inline hipError_t OwnedBuf::grow(pag_graph *g, size_t need, size_t want) {
+    if (cap >= need) return hipSuccess;
+    retire(g, p, kind);
+    p = nullptr;
+    cap = 0;
+    const hipError_t e = kind == DEVICE ? hipMalloc(&p, want) : hipHostMalloc(&p, want, kind == PINNED ? hipHostMallocDefault : hipHostMallocCoherent | hipHostMallocMapped);
+    if (e != hipSuccess) p = nullptr;
+    else cap = want;
+    return e;
+}
+// one more pinned chunk for the fetched paths (pag_reserve_walk_arena ahead of the walks, fetch_alloc when they need one)
+inline void *fetch_chunk_add(pag_graph *g, size_t bytes) {
+    OwnedBuf c(OwnedBuf::PINNED);
+    if (c.grow(g, bytes, bytes) != hipSuccess) return nullptr;
+    g->fetch_chunks.push_back(c);
+    return c.p;
+}
+
+inline void slot_free(pag_graph *g, pag_graph::Slot &sl) {
+    retire(g, sl.p, OwnedBuf::DEVICE);
+    sl.p = nullptr;
+    sl.cap = 0;
+}
+// The one way a pool slot grows.  A slot that holds `need` bytes stays as it is; any other is replaced by an array of `want`
+// bytes (each caller's own formula) whose first `keep_bytes` are the old array's.  The allocation is booked in
+// alloc_ms / bytes / calls.
+//   keep_bytes == 0: the old array goes first, so the peak is one array — after a failed allocation the slot is empty.
+//   keep_bytes != 0: allocate, copy, then let the old array go — after a failed allocation or copy the slot is as it was.
+// The copy is queued on `s` and waited for: it comes after whatever `s` wrote into the old array, which may then be freed.
+// (Not a blocking hipMemcpy: that is ordered after other streams' work only when they are blocking streams.)  The callers see to
+// it that nothing on ANOTHER stream still uses the old array — shard_comm.hip ends its exchange first; shard_serial.hip has none.
+inline int slot_grow(pag_graph *g, pag_graph::Slot &sl, size_t need, size_t want, size_t keep_bytes, hipStream_t s) {
+    if (sl.cap >= need) return PAG_OK;
+    if (want < need || keep_bytes > sl.cap || keep_bytes > want) {
+        set_error("slot_grow: need %zu, want %zu, keep %zu of a slot of %zu bytes", need, want, keep_bytes, sl.cap);
+        return PAG_EINVAL;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!keep_bytes) slot_free(g, sl);
+    void *p = nullptr;
+    hipError_t e = hipMalloc(&p, want);
+    g->alloc_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    g->alloc_bytes += want;
+    g->alloc_calls += 1;
+    if (e != hipSuccess) {
+        set_error("hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
+        return PAG_ENOMEM;
+    }
+    if (keep_bytes) {
+        e = hipMemcpyAsync(p, sl.p, keep_bytes, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            hipFree(p);
+            set_error("a slot's first %zu bytes could not be moved: %s", keep_bytes, hipGetErrorString(e));
+            return PAG_EFAULT;
+        }
+        slot_free(g, sl);
+    }
+    sl.p = p;
+    sl.cap = want;
+    return PAG_OK;
+}
+
 struct DevBuf {  // a view of one pool slot of the handle (never frees; pag_destroy does)
     pag_graph *g = nullptr;
     pag_graph::Slot *sl = nullptr;
@@ -120,31 +222,15 @@ struct DevBuf {  // a view of one pool slot of the handle (never frees; pag_dest
     DevBuf() = default;
     DevBuf(pag_graph *gg, ps::Id s) : g(gg), sl(&gg->pool[s]) {}
     DevBuf(pag_graph *gg, pag_graph::Slot *slot) : g(gg), sl(slot) {}
+    int alloc_keeping(size_t bytes, size_t keep_bytes, size_t want) {
+        const int rc = slot_grow(g, *sl, bytes, want, keep_bytes, g->stream);
+        p = sl->p;
+        return rc;
+    }
     int alloc(size_t bytes) {
         if (bytes == 0) bytes = 16;
-        if (sl->cap < bytes) {
-            const auto t0 = std::chrono::steady_clock::now();
-            if (sl->p) {
-                if (g->defer_free) g->deferred.push_back(sl->p);
-                else hipFree(sl->p);
-            }
-            sl->p = nullptr;
-            sl->cap = 0;
-            // (room to grow without another hipMalloc: an eighth, at most 512 MB — an eighth of every slot was 25 GB of a 90 Mb block at 30x)
-            size_t want = bytes + std::min<size_t>(bytes / 8, (size_t)512 << 20) + 256;
-            hipError_t e = hipMalloc(&sl->p, want);
-            g->alloc_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            g->alloc_bytes += want;
-            g->alloc_calls += 1;
-            if (e != hipSuccess) {
-                sl->p = nullptr;
-                pagdev::set_error("hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
-                return PAG_ENOMEM;
-            }
-            sl->cap = want;
-        }
-        p = sl->p;
-        return PAG_OK;
+        // (room to grow without another hipMalloc: an eighth, at most 512 MB — an eighth of every slot was 25 GB of a 90 Mb block at 30x)
+        return alloc_keeping(bytes, 0, bytes + std::min<size_t>(bytes / 8, (size_t)512 << 20) + 256);
     }
     template <typename T>
     T *as() const {

@@ -29,6 +29,7 @@
 #include <thread>
 #include <vector>
 
+#include "dev_call.hpp"
 #include "pag_graph_impl.hpp"
 
 namespace {
@@ -637,23 +638,6 @@ struct XchgGuard {  // (an error return between begin and end must not leave a j
         if (X.ev1) hipEventDestroy(X.ev1);
     }
 };
-struct DevTemp {  // device arrays of one call, freed when it returns
-    std::vector<void *> ptrs;
-    void *get(size_t bytes) {
-        void *p = nullptr;
-        if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) {
-            pagdev::set_error("hipMalloc(%zu) failed in the sharded build", bytes);
-            return nullptr;
-        }
-        ptrs.push_back(p);
-        return p;
-    }
-    void release() {
-        for (void *p : ptrs) hipFree(p);
-        ptrs.clear();
-    }
-    ~DevTemp() { release(); }
-};
 }  // namespace
 
 extern "C" {
@@ -708,7 +692,7 @@ static int shard_run(pag_graph *g, pag_comm *c, const pag_build_input *in, const
         void *recv[4] = {nullptr, nullptr, nullptr, nullptr};  // what the ranks sent of theirs
     };
     std::vector<ChunkBufs> cb((size_t)C);
-    DevTemp tmp;
+    DevCall tmp("pag_shard_run"), sent("pag_shard_run");  // the chunks as received; this rank's copies of them on their way out
     Xchg X;
     XchgGuard xguard{X};
     double t_extract = 0, t_xfer = 0, t_loop0 = 0, t_hidden = 0;
@@ -726,7 +710,9 @@ static int shard_run(pag_graph *g, pag_comm *c, const pag_build_input *in, const
             const void *src[4] = {part.tkey, part.tval, part.ekey, part.eval};
             for (int a = 0; a < 4; ++a) {
                 const uint64_t n = a < 2 ? Tc : Ec;
-                if (!(cb[ch].send[a] = tmp.get((n + 1) * ps::STREAM_ESZ[a]))) return PAG_ENOMEM;
+                char *q = nullptr;
+                if ((rc = sent.alloc(&q, (n + 1) * ps::STREAM_ESZ[a]))) return rc;
+                cb[ch].send[a] = q;
                 if (n) PAG_HIP_TRY(hipMemcpyAsync(cb[ch].send[a], src[a], n * ps::STREAM_ESZ[a], hipMemcpyDeviceToDevice, s));
             }
             PAG_HIP_TRY(hipStreamSynchronize(s));
@@ -751,7 +737,9 @@ static int shard_run(pag_graph *g, pag_comm *c, const pag_build_input *in, const
                     arrs[a].rb[r] = (cnt(ch, r, me, q0) + cnt(ch, r, me, q0 + 1)) * ps::STREAM_ESZ[a];
                     tot += arrs[a].rb[r];
                 }
-                if (!(cb[ch].recv[a] = tmp.get(tot + ps::STREAM_ESZ[a]))) return PAG_ENOMEM;
+                char *q = nullptr;
+                if ((rc = tmp.alloc(&q, tot + ps::STREAM_ESZ[a]))) return rc;
+                cb[ch].recv[a] = q;
                 arrs[a].send = cb[ch].send[a];
                 arrs[a].recv = cb[ch].recv[a];
             }
@@ -771,14 +759,7 @@ static int shard_run(pag_graph *g, pag_comm *c, const pag_build_input *in, const
             t1 += cnt(ch, r, me, 0);
             e1 += cnt(ch, r, me, 2);
         }
-    for (int ch = 0; ch < C; ++ch)  // (the chunks' send copies are done with)
-        for (int a = 0; a < 4; ++a) {
-            auto it = std::find(tmp.ptrs.begin(), tmp.ptrs.end(), cb[ch].send[a]);
-            if (it != tmp.ptrs.end()) {
-                hipFree(*it);
-                tmp.ptrs.erase(it);
-            }
-        }
+    sent.release();  // (the chunks' send copies are done with)
     DevBuf b_lk(g, ps::OWN_TK), b_lv(g, ps::OWN_TV), b_lek(g, ps::OWN_EK), b_lev(g, ps::OWN_EV);
     if ((rc = b_lk.alloc((nT + 1) * 4)) || (rc = b_lv.alloc((nT + 1) * 8)) || (rc = b_lek.alloc((nE + 1) * 4)) || (rc = b_lev.alloc((nE + 1) * 8))) return rc;
     mark(1);
@@ -844,7 +825,7 @@ static int shard_run(pag_graph *g, pag_comm *c, const pag_build_input *in, const
         };
         std::vector<std::vector<void *>> piece((size_t)W, std::vector<void *>(NA, nullptr));  // [owner][array]
         std::vector<uint64_t> piece_t(W, 0), piece_e(W, 0);
-        DevTemp rtmp;
+        DevCall rtmp("pag_shard_run");
         Xchg X;
         XchgGuard xguard{X};
         const double tl0 = now_s();
@@ -861,17 +842,7 @@ static int shard_run(pag_graph *g, pag_comm *c, const pag_build_input *in, const
                 const uint64_t need = (at[a] + n + 1) * esz[a];
                 if (b.sl->cap < need) {
                     // (grown with the old contents kept; an exchange that still reads the old array is waited for first)
-                    if ((rc = xchg_end(X))) return rc;
-                    void *np = nullptr;
-                    const size_t want = need + need / 2 + 256;
-                    PAG_HIP_TRY(hipMalloc(&np, want));
-                    if (b.sl->p && at[a]) PAG_HIP_TRY(hipMemcpy(np, b.sl->p, at[a] * esz[a], hipMemcpyDeviceToDevice));
-                    if (b.sl->p) {  // (as DevBuf::alloc: nothing is freed under a resident walker grid)
-                        if (g->defer_free) g->deferred.push_back(b.sl->p);
-                        else hipFree(b.sl->p);
-                    }
-                    b.sl->p = np;
-                    b.sl->cap = want;
+                    if ((rc = xchg_end(X)) || (rc = b.alloc_keeping(need, at[a] * esz[a], need + need / 2 + 256))) return rc;
                     if (piece[(size_t)me][a]) piece[(size_t)me][a] = b.sl->p;  // (this rank's own piece lies at the front of these arrays)
                 }
                 if (n) PAG_HIP_TRY(hipMemcpyAsync((char *)b.sl->p + at[a] * esz[a], from.p[a], n * esz[a], hipMemcpyDeviceToDevice, s));
@@ -899,7 +870,9 @@ static int shard_run(pag_graph *g, pag_comm *c, const pag_build_input *in, const
             std::vector<XchgArr> xa(NA);
             for (int a = 0; a < NA; ++a) {
                 const uint64_t n_out = a < NT ? sel[dst].n_t : sel[dst].n_e, n_in = a < NT ? piece_t[(size_t)src] : piece_e[(size_t)src];
-                if (!(piece[(size_t)src][a] = rtmp.get((n_in + 1) * esz[a]))) return PAG_ENOMEM;
+                char *q = nullptr;
+                if ((rc = rtmp.alloc(&q, (n_in + 1) * esz[a]))) return rc;
+                piece[(size_t)src][a] = q;
                 xa[a].sb.assign(W, 0);
                 xa[a].rb.assign(W, 0);
                 xa[a].sb[(size_t)dst] = n_out * esz[a];
@@ -939,20 +912,9 @@ static int shard_run(pag_graph *g, pag_comm *c, const pag_build_input *in, const
         for (int a = 0; a < NA; ++a) {
             const uint64_t n = a < NT ? sel[d].n_t : sel[d].n_e;
             DevBuf b(g, send_slot(a));
-            // (grown with the old contents kept: DevBuf::alloc replaces the allocation)
+            // (grown with the old contents kept)
             const uint64_t need = (at[a] + n + 1) * esz[a];
-            if (b.sl->cap < need) {
-                void *np = nullptr;
-                const size_t want = need + need / 2 + 256;
-                PAG_HIP_TRY(hipMalloc(&np, want));
-                if (b.sl->p && at[a]) PAG_HIP_TRY(hipMemcpy(np, b.sl->p, at[a] * esz[a], hipMemcpyDeviceToDevice));
-                if (b.sl->p) {
-                    if (g->defer_free) g->deferred.push_back(b.sl->p);
-                    else hipFree(b.sl->p);
-                }
-                b.sl->p = np;
-                b.sl->cap = want;
-            }
+            if ((rc = b.alloc_keeping(need, at[a] * esz[a], need + need / 2 + 256))) return rc;
             if (n) PAG_HIP_TRY(hipMemcpyAsync((char *)b.sl->p + at[a] * esz[a], src.p[a], n * esz[a], hipMemcpyDeviceToDevice, s));
             at[a] += n;
         }

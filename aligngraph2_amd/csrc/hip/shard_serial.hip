@@ -33,51 +33,14 @@ namespace {
 
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-// room for `need` bytes in a slot whose first `used` bytes are kept (DevBuf::alloc drops the contents when it grows a slot)
-int grow_keeping(pag_graph *g, ps::Id id, size_t used, size_t need, size_t hint) {
-    pag_graph::Slot &sl = g->pool[id];
-    if (sl.p && sl.cap >= need) return PAG_OK;
-    const auto t0 = std::chrono::steady_clock::now();
-    const size_t want = std::max(need, hint) + 256;
-    void *p = nullptr;
-    hipError_t e = hipMalloc(&p, want);
-    g->alloc_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    g->alloc_bytes += want;
-    g->alloc_calls += 1;
-    if (e != hipSuccess) {
-        set_error("hipMalloc(%zu) failed: %s (a region of a serial-rank run)", want, hipGetErrorString(e));
-        return PAG_ENOMEM;
-    }
-    if (used && sl.p) {
-        e = hipMemcpyAsync(p, sl.p, used, hipMemcpyDeviceToDevice, g->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
-        if (e != hipSuccess) {
-            hipFree(p);
-            set_error("a region of a serial-rank run could not be moved: %s", hipGetErrorString(e));
-            return PAG_EFAULT;
-        }
-    }
-    if (sl.p) hipFree(sl.p);
-    sl.p = p;
-    sl.cap = want;
-    return PAG_OK;
-}
-
-void free_slot(pag_graph::Slot &sl) {
-    if (sl.p) hipFree(sl.p);
-    sl.p = nullptr;
-    sl.cap = 0;
-}
-
 // what the traversal of the turn before took: its slots (graph view, successor records, walk session) and the walk arena, which
 // pag_travel sizes again from what is free once the build is released (as it did for the prototype's fresh handles)
 void release_traversal(pag_graph *g) {
     hipStreamSynchronize(g->stream);
     g->tg_ready = false;
-    for (int i = ps::TG_NCODE; i <= ps::WALK_SEQS; ++i) free_slot(g->pool[i]);
-    if (g->walk_arena) hipFree(g->walk_arena);
-    g->walk_arena = nullptr;
-    g->walk_arena_cap = g->walk_arena_used = 0;
+    for (int i = ps::TG_NCODE; i <= ps::WALK_SEQS; ++i) slot_free(g, g->pool[i]);
+    g->walk_arena.release();
+    g->walk_arena_used = 0;
 }
 
 // pag_shard_release_build that keeps the arrays of a device-resident input (pag_prepare's outputs live in the handle's pool;
@@ -99,7 +62,7 @@ void release_build_keeping(pag_graph *g, const pag_build_input *in) {
         const char *lo = (const char *)sl.p, *hi = lo + sl.cap;
         bool used = false;
         for (const void *p : keep) used = used || (p && (const char *)p >= lo && (const char *)p < hi);
-        if (!used) free_slot(sl);
+        if (!used) slot_free(g, sl);
     }
 }
 
@@ -213,8 +176,9 @@ int serial_turn(pag_graph *g, const pag_build_input *in, const pag_region *regio
             const size_t esz = (size_t)ps::GRAPH_ESZ[a], have = (size_t)(tup ? at_t : at_e) * esz, add = (size_t)(tup ? sel.n_t : sel.n_e) * esz;
             const size_t need = have + add + esz;
             const size_t guess = (have + add) / (o + 1) * n;
-            if ((rc = grow_keeping(g, ps::family(ps::IMPORT, a), have, need, guess + guess / 16))) return rc;
-            if (add) PAG_HIP_TRY(hipMemcpyAsync((char *)g->pool[ps::family(ps::IMPORT, a)].p + have, from.p[a], add, hipMemcpyDeviceToDevice, g->stream));
+            DevBuf imp(g, ps::family(ps::IMPORT, a));
+            if ((rc = imp.alloc_keeping(need, have, std::max(need, guess + guess / 16) + 256))) return rc;
+            if (add) PAG_HIP_TRY(hipMemcpyAsync((char *)imp.p + have, from.p[a], add, hipMemcpyDeviceToDevice, g->stream));
             st.region_bytes += add;
         }
         PAG_HIP_TRY(hipStreamSynchronize(g->stream));

@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "dev_call.hpp"
 #include "pag_device.hpp"
 #include "pag_travel.hpp"
 
@@ -155,32 +156,17 @@ __device__ __forceinline__ void tile_flush(const unsigned char *stage, unsigned 
     }
 }
 
-// ---- pag_render_dump_lines / pag_render_path_sequence: the stream and the device buffers of one such call; the caller's
-//      current device is put back at every exit
-struct TextCall {
-    hipStream_t s = nullptr;
-    std::vector<void *> bufs;
-    int back = -1;
-    void *rec = nullptr, *tab = nullptr;  // the records, the tables' blob (dump_tables_at)
-    ~TextCall() {
-        for (void *p : bufs) hipFree(p);
-        if (s) hipStreamDestroy(s);
-        if (back >= 0) (void)hipSetDevice(back);
-    }
-    int alloc(void **p, size_t bytes) {
-        PAG_HIP_TRY(hipMalloc(p, bytes));
-        bufs.push_back(*p);
-        return PAG_OK;
-    }
+// ---- pag_render_dump_lines / pag_render_path_sequence: what such a call has on top of its DevCall (a non-blocking stream; the
+//      caller's current device is put back at every exit)
+struct TextCall : DevCall {
+    pag_path_node *rec = nullptr;  // the records
+    uint32_t *tab = nullptr;       // the tables' blob (dump_tables_at)
+    explicit TextCall(const char *w) : DevCall(w) {}
     // the device chosen, the stream, room for the records and the tables
     int begin(int device, uint64_t n, const std::vector<uint32_t> &blob) {
-        int caller_device = -1;
-        if (hipGetDevice(&caller_device) != hipSuccess) caller_device = -1, (void)hipGetLastError();
-        PAG_HIP_TRY(hipSetDevice(device));
-        back = caller_device == device ? -1 : caller_device;
-        PAG_HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        const int rc = alloc(&rec, n * sizeof(pag_path_node));
-        return rc ? rc : alloc(&tab, blob.size() * 4 + 16);
+        int rc = open(device, true, hipStreamNonBlocking);
+        if (!rc) rc = alloc(&rec, n);
+        return rc ? rc : alloc(&tab, blob.size(), 16);
     }
     // ... and, when every buffer of the call has been allocated, their upload
     int upload(const pag_path_node *records, uint64_t n, const std::vector<uint32_t> &blob) {

@@ -1,59 +1,18 @@
 // What the test hooks on constructed graphs share (include/pagraph_debug.h; defined at the foot of k5_walk_aux.hip,
-// k5_view.hip and k5_travel.hip): the device buffers of one hook call, and the upload of a pag_debug_trav_graph into a TravGraph.  Nothing in the
-// product includes this.
+// k5_view.hip and k5_travel.hip): the upload of a pag_debug_trav_graph into a TravGraph, in the buffers of the hook's DevCall
+// (dev_call.hpp).  Nothing in the product includes this.
 #pragma once
 #include <vector>
 
+#include "dev_call.hpp"
 #include "pag_device.hpp"
 #include "pag_travel.hpp"
 #include "pagraph_debug.h"
 
 namespace pagdev {
 
-// the device, stream and buffers of one hook call; everything is given back when it goes out of scope
-struct HookDev {
-    int before = 0;
-    bool switched = false;
-    hipStream_t s = nullptr;
-    std::vector<void *> bufs;
-    int open(int device) {
-        PAG_HIP_TRY(hipGetDevice(&before));
-        PAG_HIP_TRY(hipSetDevice(device));
-        switched = true;
-        PAG_HIP_TRY(hipStreamCreate(&s));
-        return PAG_OK;
-    }
-    // n elements of `host` (null or n == 0: nothing is copied) in a buffer of its own with `pad` zeroed bytes behind them
-    template <typename T>
-    int up(const T *host, uint64_t n, T **out, size_t pad = 64) {
-        void *p = nullptr;
-        PAG_HIP_TRY(hipMalloc(&p, n * sizeof(T) + pad));
-        bufs.push_back(p);
-        PAG_HIP_TRY(hipMemsetAsync((char *)p + n * sizeof(T), 0, pad, s));
-        if (host && n) PAG_HIP_TRY(hipMemcpyAsync(p, host, n * sizeof(T), hipMemcpyHostToDevice, s));
-        *out = (T *)p;
-        return PAG_OK;
-    }
-    template <typename T>
-    int down(T *host, const T *dev, uint64_t n) {
-        if (n) PAG_HIP_TRY(hipMemcpyAsync(host, dev, n * sizeof(T), hipMemcpyDeviceToHost, s));
-        return PAG_OK;
-    }
-    int finish() {
-        PAG_HIP_TRY(hipGetLastError());
-        PAG_HIP_TRY(hipStreamSynchronize(s));
-        return PAG_OK;
-    }
-    ~HookDev() {
-        if (s) hipStreamSynchronize(s);
-        for (void *p : bufs) hipFree(p);
-        if (s) hipStreamDestroy(s);
-        if (switched) hipSetDevice(before);
-    }
-};
-
 // the arrays of g that are given, on the device; refuses a graph whose own indices point outside it
-inline int hook_upload_graph(HookDev &D, const pag_debug_trav_graph *g, TravGraph *G) {
+inline int hook_upload_graph(DevCall &D, const pag_debug_trav_graph *g, TravGraph *G) {
     if (!g || g->k < 1 || g->k > 16 || g->n_pos >= 0xFFFFFFF0ull || g->n_nodes >= 0xFFFFFFF0ull) return PAG_EINVAL;
     const uint64_t nn = g->n_nodes, np = g->n_pos;
     if (g->npos_off) {

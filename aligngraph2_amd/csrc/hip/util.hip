@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "dev_call.hpp"
 #include "pag_device.hpp"
 #include "pagraph_debug.h"
 
@@ -314,35 +315,20 @@ extern "C" int pag_debug_cov_filter(const pag_aln *aln, uint64_t n_aln, const pa
     if (n_aln == 0) return PAG_OK;
     if (hipSetDevice(device) != hipSuccess) return PAG_ENODEV;
     const size_t tmp_bytes = cov_tmp_bytes(refs, n_refs);
+    DevCall D("pag_debug_cov_filter");  // (the device stays current)
     pag_aln *d_aln = nullptr;
     pag_ref *d_refs = nullptr;
     uint8_t *d_ok = nullptr;
-    void *d_tmp = nullptr;
-    int rc = PAG_OK;
-    hipError_t e = hipMalloc((void **)&d_aln, n_aln * sizeof(pag_aln));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_refs, (n_refs ? n_refs : 1) * sizeof(pag_ref));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_ok, n_aln + GUARD);
-    if (e == hipSuccess) e = hipMalloc(&d_tmp, tmp_bytes);
-    if (e != hipSuccess) rc = PAG_ENOMEM;
-    if (e == hipSuccess) e = hipMemcpy(d_aln, aln, n_aln * sizeof(pag_aln), hipMemcpyHostToDevice);
-    if (e == hipSuccess && n_refs) e = hipMemcpy(d_refs, refs, n_refs * sizeof(pag_ref), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(d_ok, 0xA5, n_aln + GUARD);
-    if (e == hipSuccess) {
-        rc = launch_cov_filter(d_aln, n_aln, d_refs, refs, n_refs, cov_filter, d_ok, d_tmp, tmp_bytes, nullptr);
-        e = hipDeviceSynchronize();
-    }
+    char *d_tmp = nullptr;
     uint8_t guard[GUARD];
-    if (e == hipSuccess && rc == PAG_OK) e = hipMemcpy(ok, d_ok, n_aln, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rc == PAG_OK) e = hipMemcpy(guard, d_ok + n_aln, GUARD, hipMemcpyDeviceToHost);
-    hipFree(d_aln);
-    hipFree(d_refs);
-    hipFree(d_ok);
-    hipFree(d_tmp);
-    if (rc != PAG_OK) return rc;
-    if (e != hipSuccess) {
-        set_error("pag_debug_cov_filter: %s", hipGetErrorString(e));
-        return PAG_EFAULT;
-    }
+    int rc;
+    if ((rc = D.open(device, false, hipStreamDefault)) || (rc = D.up(aln, n_aln, &d_aln, 0)) || (rc = D.up(refs, n_refs, &d_refs, n_refs ? 0 : sizeof(pag_ref))) ||
+        (rc = D.alloc(&d_ok, n_aln, GUARD)) || (rc = D.alloc(&d_tmp, tmp_bytes)))
+        return rc;
+    PAG_HIP_TRY(hipMemsetAsync(d_ok, 0xA5, n_aln + GUARD, D.s));
+    if ((rc = launch_cov_filter(d_aln, n_aln, d_refs, refs, n_refs, cov_filter, d_ok, d_tmp, tmp_bytes, D.s)) || (rc = D.down(ok, (const uint8_t *)d_ok, n_aln)) ||
+        (rc = D.down(guard, (const uint8_t *)d_ok + n_aln, GUARD)) || (rc = D.finish()))
+        return rc;
     for (size_t i = 0; i < GUARD; ++i)
         if (guard[i] != 0xA5) {
             set_error("pag_debug_cov_filter: byte %zu behind ok[n_aln] was written", i);

@@ -55,23 +55,14 @@ struct WalkJobs {
         lap_t = t;
     }
     // pinned host staging area (grown, kept in the handle): packed job results on their way in, uploads on their way out
-    std::vector<void *> pinned_parked;  // (freeing host memory synchronises the device: never while the walker grid is resident)
+    // (freeing host memory synchronises the device: while the walker grid is resident the old area is parked, OwnedBuf::grow)
     void *pinned(size_t bytes) {
-        if (g->pin_bytes < bytes) {
-            if (g->pin_host) {
-                if (g->defer_free) pinned_parked.push_back(g->pin_host);
-                else hipHostFree(g->pin_host);
-            }
-            g->pin_host = nullptr;
-            g->pin_bytes = 0;
-            const size_t want = bytes + bytes / 4 + (1u << 20);
-            if (hipHostMalloc(&g->pin_host, want, hipHostMallocDefault) != hipSuccess) {
-                set_error("pag_travel: hipHostMalloc(%zu) failed", want);
-                return nullptr;
-            }
-            g->pin_bytes = want;
+        const size_t want = bytes + bytes / 4 + (1u << 20);
+        if (g->pin_host.grow(g, bytes, want) != hipSuccess) {
+            set_error("pag_travel: hipHostMalloc(%zu) failed", want);
+            return nullptr;
         }
-        return g->pin_host;
+        return g->pin_host.p;
     }
 
     // Pinned memory that keeps what it is given for the whole call: the fetched paths of finished jobs stay where the copy
@@ -81,19 +72,17 @@ struct WalkJobs {
     void *fetch_alloc(size_t bytes) {
         bytes = (bytes + 255) & ~(size_t)255;
         for (; fetch_chunk < g->fetch_chunks.size(); ++fetch_chunk, fetch_used = 0)
-            if (fetch_used + bytes <= g->fetch_chunk_bytes[fetch_chunk]) {
-                void *q = (char *)g->fetch_chunks[fetch_chunk] + fetch_used;
+            if (fetch_used + bytes <= g->fetch_chunks[fetch_chunk].cap) {
+                void *q = (char *)g->fetch_chunks[fetch_chunk].p + fetch_used;
                 fetch_used += bytes;
                 return q;
             }
-        void *q = nullptr;
         const size_t want = std::max(FETCH_CHUNK, bytes);
-        if (hipHostMalloc(&q, want, hipHostMallocDefault) != hipSuccess) {
+        void *q = fetch_chunk_add(g, want);
+        if (!q) {
             set_error("pag_travel: hipHostMalloc(%zu) failed", want);
             return nullptr;
         }
-        g->fetch_chunks.push_back(q);
-        g->fetch_chunk_bytes.push_back(want);
         fetch_used = bytes;  // (fetch_chunk is the index of the new chunk)
         return q;
     }
@@ -224,14 +213,9 @@ struct WalkJobs {
     std::atomic<uint64_t> n_adopted{0}, n_merge_fail{0}, n_leap_adopted{0}, n_leap_refused[8];
     uint64_t n_seg_jobs = 0, n_resume_jobs = 0, n_leap_jobs = 0;
     WalkerGrid walkers;
-    void shutdown_walker() {
-        if (!walkers.up) return;
-        walkers.shutdown();
-        g->defer_free = false;
-        for (void *q : g->deferred) hipFree(q);
-        g->deferred.clear();
-        for (void *q : pinned_parked) hipHostFree(q);
-        pinned_parked.clear();
+    void shutdown_walker() {  // (also with no grid up: what a call parked before it failed to launch one is released)
+        if (walkers.up) walkers.shutdown();
+        drain_deferred(g);
     }
     struct JobPlan {
         int kind, idx;
@@ -375,9 +359,9 @@ struct WalkJobs {
             DevBuf *bufs[9] = {&b_sv, &b_ss, &b_av, &b_as, &b_ts, &b_ps, &b_st, &b_tb, &b_sx};
             size_t tot = 0;
             for (size_t q = 0; q < 9; ++q) tot += (need[q] + 16 + 255) & ~(size_t)255;
-            if (g->walk_arena && g->walk_arena_used + tot <= g->walk_arena_cap) {
+            if (g->walk_arena.p && g->walk_arena_used + tot <= g->walk_arena.cap) {
                 for (size_t q = 0; q < 9; ++q) {
-                    bufs[q]->p = (char *)g->walk_arena + g->walk_arena_used;
+                    bufs[q]->p = (char *)g->walk_arena.p + g->walk_arena_used;
                     g->walk_arena_used += (need[q] + 16 + 255) & ~(size_t)255;
                 }
             } else {

@@ -45,7 +45,7 @@ struct WalkSession : WalkRounds {
             const double idle_limit_ms = cfg.idle_limit_ms;
             if (now_ms() - t_progress > idle_limit_ms) {  // no job finished for a minute: give up instead of hanging
                 uint32_t ticket[TRAV_RINGS] = {0, 0, 0};
-                hipMemcpyAsync(ticket, g->wq_next, sizeof(ticket), hipMemcpyDeviceToHost, s);
+                hipMemcpyAsync(ticket, g->wq_next.p, sizeof(ticket), hipMemcpyDeviceToHost, s);
                 hipStreamSynchronize(s);
                 set_error("pag_travel: no walk job finished within %.0f s (posted %u + %u + %u, claimed %u + %u + %u, jobs outstanding %u, walker waves started %u / left %u of %u launched)",
                           idle_limit_ms / 1000.0, n_posted[0], n_posted[1], n_posted[2], ticket[0], ticket[1], ticket[2], n_live, walkers.started(), walkers.exited(), walkers.launched);
@@ -410,16 +410,16 @@ struct WalkSession : WalkRounds {
                 const rounds::Trim trim = rounds::trim_path(base, ch.parts.front().pc[0], k);
                 const size_t at0 = trim.at0;
                 const int32_t dist = trim.dist;
-                if (P.leap && !RS[i].slot_bufs && g->walk_arena && !cfg.debug_deliver_late) {
+                if (P.leap && !RS[i].slot_bufs && g->walk_arena.p && !cfg.debug_deliver_late) {
                     // the contig is finished by this walk (splice below): nothing of it is needed on the host
                     bool on_dev = true;
                     for (const Chain::Part &pt : ch.parts) on_dev = on_dev && pt.dv && pt.ds;
                     const size_t cap = at0 + P.len, need = (cap * 8 + 255) & ~(size_t)255;
-                    TravConcatPart *cp = on_dev && g->walk_arena_used + need <= g->walk_arena_cap ? (TravConcatPart *)fetch_alloc(ch.parts.size() * sizeof(TravConcatPart)) : nullptr;
+                    TravConcatPart *cp = on_dev && g->walk_arena_used + need <= g->walk_arena.cap ? (TravConcatPart *)fetch_alloc(ch.parts.size() * sizeof(TravConcatPart)) : nullptr;
                     if (cp) {
                         CtgState::DevTail &T = cs.tail;
                         T.on = true;
-                        T.d_ids = (uint32_t *)((char *)g->walk_arena + g->walk_arena_used);
+                        T.d_ids = (uint32_t *)((char *)g->walk_arena.p + g->walk_arena_used);
                         g->walk_arena_used += need;
                         T.cap = cap;
                         T.m0 = at0;
@@ -685,9 +685,6 @@ struct WalkSession : WalkRounds {
     int finish() {
         int rc;
         shutdown_walker();
-        g->defer_free = false;
-        for (void *q : pinned_parked) hipHostFree(q);
-        pinned_parked.clear();
         t_walk = now_ms() - tw0;
         lap("walk");
         if (wtrace) {
@@ -711,7 +708,7 @@ struct WalkSession : WalkRounds {
         }
         if (timing || wdebug) {
             std::fprintf(stderr, "[timing] stitch: bookkeeping %.1f ms, paths %.1f ms, chains %.1f ms; posting jobs (all callers) %.1f ms; fetch memory: chunk %zu of %zu; walk arena: %.2f of %.2f GB used\n", t_st[0], t_st[1], t_st[2], t_st[3],
-                         fetch_chunk + 1, g->fetch_chunks.size(), g->walk_arena_used / 1e9, g->walk_arena_cap / 1e9);
+                         fetch_chunk + 1, g->fetch_chunks.size(), g->walk_arena_used / 1e9, g->walk_arena.cap / 1e9);
             std::fprintf(stderr, "[timing] leaping zone: %llu segment jobs, %llu adopted, refused by reason (unusable, no junction, not a boundary, cannot leap yet, window top, window bottom, contig-following record, coordinate-free record): %llu %llu %llu %llu %llu %llu %llu %llu\n",
                          (unsigned long long)n_leap_jobs, (unsigned long long)n_leap_adopted.load(), (unsigned long long)n_leap_refused[0].load(), (unsigned long long)n_leap_refused[1].load(), (unsigned long long)n_leap_refused[2].load(),
                          (unsigned long long)n_leap_refused[3].load(), (unsigned long long)n_leap_refused[4].load(), (unsigned long long)n_leap_refused[5].load(), (unsigned long long)n_leap_refused[6].load(), (unsigned long long)n_leap_refused[7].load());
@@ -732,16 +729,10 @@ struct WalkSession : WalkRounds {
             uint64_t tot = 0;
             for (auto &cs : st)
                 if (!cs.delivered) tot += cs.travel.size();
-            if (g->path_cap < tot + 1) {
-                if (g->path_store) hipHostFree(g->path_store);
-                g->path_store = nullptr;
-                g->path_cap = 0;
-                const size_t want = tot + tot / 8 + 1024;
-                if (hipHostMalloc((void **)&g->path_store, want * sizeof(pag_path_node), hipHostMallocDefault) != hipSuccess) {
-                    set_error("pag_travel: hipHostMalloc for %zu path records failed", want);
-                    return fail(PAG_ENOMEM);
-                }
-                g->path_cap = want;
+            const size_t want = tot + tot / 8 + 1024;
+            if (g->path_store.grow(g, (tot + 1) * sizeof(pag_path_node), want * sizeof(pag_path_node)) != hipSuccess) {
+                set_error("pag_travel: hipHostMalloc for %zu path records failed", want);
+                return fail(PAG_ENOMEM);
             }
             uint32_t *hp = (uint32_t *)pinned(tot * 8 + 256);
             if (!hp) return fail(PAG_ENOMEM);
@@ -765,23 +756,17 @@ struct WalkSession : WalkRounds {
             if (tot) {
                 PAG_HIP_TRY(hipMemcpyAsync(b_fin.p, hp, tot * 8, hipMemcpyHostToDevice, s));
                 trav_launch_gather_path(G, b_fin.as<uint32_t>(), b_fin.as<uint32_t>() + tot, tot, b_gather.as<pag_path_node>(), s);
-                PAG_HIP_TRY(hipMemcpyAsync(g->path_store, b_gather.p, tot * sizeof(pag_path_node), hipMemcpyDeviceToHost, s));
+                PAG_HIP_TRY(hipMemcpyAsync(g->path_store.p, b_gather.p, tot * sizeof(pag_path_node), hipMemcpyDeviceToHost, s));
             }
             if (scratch_bytes) {  // the dump text and the consensus sequence of those sequences: one rendering per contig, at full width (no walk is live)
-                if (g->dump_scratch_cap < scratch_bytes) {
-                    if (g->dump_scratch) PAG_HIP_TRY(hipFree(g->dump_scratch));
-                    g->dump_scratch = nullptr;
-                    g->dump_scratch_cap = 0;
-                    PAG_HIP_TRY(hipMalloc(&g->dump_scratch, scratch_bytes + scratch_bytes / 4));
-                    g->dump_scratch_cap = scratch_bytes + scratch_bytes / 4;
-                }
+                PAG_HIP_TRY(g->dump_scratch.grow(g, scratch_bytes, scratch_bytes + scratch_bytes / 4));
                 size_t sat = 0;
                 for (auto &cs : st) {
                     if (cs.delivered || cs.travel.empty()) continue;
                     const size_t slot2 = 2 * (size_t)cs.ci + (cs.forward ? 0 : 1);
                     const uint32_t *ids = b_fin.as<uint32_t>() + g->path_off[slot2];
                     auto carve = [&](size_t bytes) {
-                        void *q = (char *)g->dump_scratch + sat;
+                        void *q = (char *)g->dump_scratch.p + sat;
                         sat += bytes;
                         return q;
                     };

@@ -311,9 +311,6 @@ struct WalkRounds : WalkJobs {
 
     int fail(int rc2) {
         shutdown_walker();
-        g->defer_free = false;
-        for (void *q : pinned_parked) hipHostFree(q);
-        pinned_parked.clear();
         // deliveries made while the walks ran (gather kernels writing pinned chunks the next call reuses) must have landed,
         // and nothing of a failed call may be handed out as a path
         if (g->deliver_stream) hipStreamSynchronize(g->deliver_stream);
@@ -378,15 +375,9 @@ struct WalkRounds : WalkJobs {
         for (uint64_t r = 0; want_seqs && r < n_refs; ++r) want_seqs = refs->len[r] == ref_len[r];
         if ((!want_dumps && !want_seqs) || !dump_tables_build(ctgs->len, ctgs->n_seqs, ref_len, n_refs, dump_blob)) return PAG_OK;
         const size_t bytes = dump_blob.size() * 4 + 16;
-        if (g->dump_tables_cap < bytes) {
-            if (g->dump_tables) PAG_HIP_TRY(hipFree(g->dump_tables));
-            g->dump_tables = nullptr;
-            g->dump_tables_cap = 0;
-            PAG_HIP_TRY(hipMalloc(&g->dump_tables, bytes + bytes / 4));
-            g->dump_tables_cap = bytes + bytes / 4;
-        }
-        if (!dump_blob.empty()) PAG_HIP_TRY(hipMemcpyAsync(g->dump_tables, dump_blob.data(), dump_blob.size() * 4, hipMemcpyHostToDevice, s));
-        dump_tab = dump_tables_at((const uint32_t *)g->dump_tables, ctgs->n_seqs, n_refs);
+        PAG_HIP_TRY(g->dump_tables.grow(g, bytes, bytes + bytes / 4));
+        if (!dump_blob.empty()) PAG_HIP_TRY(hipMemcpyAsync(g->dump_tables.p, dump_blob.data(), dump_blob.size() * 4, hipMemcpyHostToDevice, s));
+        dump_tab = dump_tables_at(g->dump_tables.as<uint32_t>(), ctgs->n_seqs, n_refs);
         dump_bound = dump_line_bound(k, dump_blob, ctgs->n_seqs, n_refs);
         render = want_dumps;
         if (want_seqs) {
@@ -405,8 +396,8 @@ struct WalkRounds : WalkJobs {
     }
     size_t render_scratch_bytes(size_t m) const { return ((render ? 1 : 0) + (render_seq ? 1 : 0)) * text_scratch_bytes(m); }
     void *arena_scratch(size_t need) {  // (nullptr: no room — that contig's text is left to the caller)
-        if (!g->walk_arena || g->walk_arena_used + need > g->walk_arena_cap) return nullptr;
-        void *q = (char *)g->walk_arena + g->walk_arena_used;
+        if (!g->walk_arena.p || g->walk_arena_used + need > g->walk_arena.cap) return nullptr;
+        void *q = (char *)g->walk_arena.p + g->walk_arena_used;
         g->walk_arena_used += need;
         return q;
     }
@@ -475,7 +466,7 @@ struct WalkRounds : WalkJobs {
         if (cfg.debug_deliver_late) return PAG_OK;
         const size_t n = cs.travel.size();
         const size_t need = ((n * 8 + 255) & ~(size_t)255) + 512 + render_scratch_bytes(n);
-        if (!g->walk_arena || g->walk_arena_used + need > g->walk_arena_cap) return PAG_OK;
+        if (!g->walk_arena.p || g->walk_arena_used + need > g->walk_arena.cap) return PAG_OK;
         rounds::filter_travel(cs.travel, cs.finalLeap, mapper, cs.ci, startSplit);
         const size_t m = cs.travel.size();
         const size_t slot2 = 2 * (size_t)cs.ci + (cs.forward ? 0 : 1);
@@ -491,7 +482,7 @@ struct WalkRounds : WalkJobs {
             hp[x] = cs.travel[x].u;
             hp[m + x] = (uint32_t)cs.travel[x].step;
         }
-        uint32_t *d_ids = (uint32_t *)((char *)g->walk_arena + g->walk_arena_used);
+        uint32_t *d_ids = (uint32_t *)((char *)g->walk_arena.p + g->walk_arena_used);
         g->walk_arena_used += (m * 8 + 255) & ~(size_t)255;
         // A stream of its own (behind this work on stream s the fetches of finished jobs would wait), and the gather kernel
         // writes the records straight into the pinned host array: a device-to-host copy of 32 bytes per vertex would
@@ -685,21 +676,15 @@ struct WalkRounds : WalkJobs {
             if (cfg.debug_ring) QCAP = (uint32_t)cfg.debug_ring;  // tests: a ring far smaller than a round
         }
         const size_t q_need = 256 + NR * (size_t)QCAP * (sizeof(TravPosted) + sizeof(TravJobOut) + sizeof(uint32_t)) + 256;
-        if (g->wq_bytes < q_need) {
-            if (g->wq_host) hipHostFree(g->wq_host);
-            g->wq_host = nullptr;
-            g->wq_bytes = 0;
-            PAG_HIP_TRY(hipHostMalloc(&g->wq_host, q_need, hipHostMallocCoherent | hipHostMallocMapped));
-            g->wq_bytes = q_need;
-        }
-        if (!g->wq_next) PAG_HIP_TRY(hipMalloc((void **)&g->wq_next, 256));
-        hq = (TravQueue *)g->wq_host;
-        hjobs = (TravPosted *)((char *)g->wq_host + 256);
+        PAG_HIP_TRY(g->wq_host.grow(g, q_need, q_need));
+        PAG_HIP_TRY(g->wq_next.grow(g, 256, 256));
+        hq = g->wq_host.as<TravQueue>();
+        hjobs = (TravPosted *)(g->wq_host.as<char>() + 256);
         houts = (TravJobOut *)(hjobs + NR * (size_t)QCAP);
         hdone = (uint32_t *)(houts + NR * (size_t)QCAP);
-        std::memset(g->wq_host, 0, 256);
+        std::memset(g->wq_host.p, 0, 256);
         std::memset(hdone, 0, NR * (size_t)QCAP * sizeof(uint32_t));
-        PAG_HIP_TRY(hipMemsetAsync(g->wq_next, 0, 256, s));
+        PAG_HIP_TRY(hipMemsetAsync(g->wq_next.p, 0, 256, s));
         PAG_HIP_TRY(hipStreamSynchronize(s));
         t_walk0 = now_ms();
         use_pieces = cfg.pieces;
@@ -736,15 +721,10 @@ struct WalkRounds : WalkJobs {
             }
             size_t free_b = 0, total_b = 0;
             const size_t sharers = env_device_sharers();
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) want = std::min(want, (free_b + g->walk_arena_cap) * 2 / 5 / sharers);
-            if (g->walk_arena_cap < want / 10 * 7) {  // (an arena that is there — pag_reserve_walk_arena, an earlier call — is kept
-                                                      // unless it is much too small: what does not fit goes to the slots)
-                if (g->walk_arena) hipFree(g->walk_arena);
-                g->walk_arena = nullptr;
-                g->walk_arena_cap = 0;
-                if (hipMalloc(&g->walk_arena, want) == hipSuccess) g->walk_arena_cap = want;
-                else g->walk_arena = nullptr;  // (the slots do all the work then)
-            }
+            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) want = std::min(want, (free_b + g->walk_arena.cap) * 2 / 5 / sharers);
+            // (an arena that is there — pag_reserve_walk_arena, an earlier call — is kept unless it is much too small: what does
+            // not fit goes to the slots; so does everything when there is no memory for a new one)
+            if (g->walk_arena.cap < want / 10 * 7 && g->walk_arena.grow(g, want, want) != hipSuccess) (void)hipGetLastError();
             g->walk_arena_used = 0;
         }
         lap("arena");

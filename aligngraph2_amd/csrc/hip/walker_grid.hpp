@@ -125,7 +125,7 @@ struct WalkerGrid {
         const auto tq1 = std::chrono::steady_clock::now();
         const bool drained = hipStreamQuery(st) == hipSuccess;
         (void)hipGetLastError();
-        trav_launch_walk_persistent(G, jobs, outs, done, q, g->wq_next, cap, k, n, idle_ticks, st);
+        trav_launch_walk_persistent(G, jobs, outs, done, q, g->wq_next.as<uint32_t>(), cap, k, n, idle_ticks, st);
         if (trace) {
             const auto tq2 = std::chrono::steady_clock::now();
             std::fprintf(stderr, "[trace] walker launch %u: %u waves on stream %p (%s, pool of %zu), have %u, picking the stream %.3f ms, the launch call %.3f ms\n", launches, n, (void *)st,

@@ -28,6 +28,17 @@ int pag_debug_trav_vertices(const pag_graph *g, uint32_t *code, uint64_t *pos);
 /* raw emitted streams of the last pag_process (needs PAG_DEBUG_KEEP_STREAMS=1) */
 int pag_debug_stream_sizes(const pag_graph *g, uint64_t *n_tuples, uint64_t *n_edges);
 int pag_debug_streams(const pag_graph *g, uint32_t *tkey, uint64_t *tval, uint32_t *ekey, uint64_t *eval);
+/* The grow rule of the handle's pool slots (slot_grow, pag_graph_impl.hpp) on one slot of a SCRATCH handle (pag_create; nothing
+ * else of it is used), step by step.  steps[n_steps] rows of four u64 (need, want, keep, op):
+ *   op 0: the slot grown to hold `need` bytes — a new array of `want` bytes whose first `keep` are the old one's, unless the slot
+ *         holds `need` already;  op 1: the same while frees are deferred (the replaced array is parked, not freed)
+ *   op 2: the parked arrays are released;  op 3: byte i of the slot set to (uint8_t)(i * 7 + need), all of its capacity;
+ *   op 4: the slot freed
+ * out[n_steps] rows of five u64, the state after the step: the step's return code (a PAG_* value, sign-extended), the slot's
+ * pointer, its capacity, the number of parked arrays, and 1 when this step parked the replaced array and its first `keep` bytes
+ * still read the same as the new one's.  kept[n_steps * kept_stride]: row i holds the first min(keep, kept_stride) bytes of the
+ * slot as read back after a successful op 0 / 1 with keep != 0. */
+int pag_debug_slot_grow(pag_graph *g, const uint64_t *steps, uint32_t n_steps, uint64_t *out, uint8_t *kept, uint64_t kept_stride);
 /* the coverage filter's kernel on records in host memory: ok[n_aln] */
 int pag_debug_cov_filter(const pag_aln *aln, uint64_t n_aln, const pag_ref *refs, uint64_t n_refs, uint32_t cov_filter,
                          uint8_t *ok, int device);
