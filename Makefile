@@ -165,6 +165,12 @@ tests/harness/bin/cns_rows_sanitized: tests/harness/cns_rows_main.cpp $(HIP_DIR)
 	@mkdir -p tests/harness/bin
 	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=all -I$(HIP_DIR) -o $@ $<
 
+# the host half of pag_find_all_batch (find_plan.hpp: plain C++; the descriptors' checks and the cut into tiles), a program of its own
+# under the address and undefined-behaviour sanitizers (host code only; built and run by tests/test_find_rule.py)
+tests/harness/bin/find_plan_sanitized: tests/harness/find_plan_main.cpp $(HIP_DIR)/find_plan.hpp
+	@mkdir -p tests/harness/bin
+	$(CXX) -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=all -I$(HIP_DIR) -o $@ $<
+
 # bin/pa_cns itself (its host code: the ingests, the flat backend, the batch engine) as a program of its own under the address and
 # undefined-behaviour sanitizers (built and run by tests/test_pa_cns_batch.py on a manifest of jobs, flat backend)
 tests/harness/bin/pa_cns_sanitized: $(HOST_DIR)/pa_cns_main.cpp $(HOST_DIR)/seq_db.cpp $(wildcard $(HOST_DIR)/*.hpp) $(HIP_DIR)/cns_graph.hpp $(HIP_DIR)/cns_rows.hpp include/pagraph_hip.h

@@ -118,6 +118,48 @@ def successors_batch(hip, g, codes, pos, deviation, error_rate):
     return off, status, records
 
 
+def find_all_batch(hip, g, packed, byte_off, lengths, reverse=None):
+    """pag_find_all_batch (include/pagraph_hip.h) for the sequences (byte_off[i], lengths[i]) of the 2-bit packed array `packed`
+    (uint8, laid out as pag_seqs says; the 16 bytes of padding are added here) in the finished graph of handle `g` of the bound
+    library `hip`; reverse[i] != 0 searches sequence i's reverse strand.  A sizing call, then the real one.  Returns
+    (hit_off, hits, vertices): hit_off[n + 1] uint64, hits hit_off[-1] entries of capi.PagFindHit as a numpy record array (offset,
+    code, first, n_pos), the hits of sequence i at hits[hit_off[i]:hit_off[i + 1]], vertices of capi.PagFindVertex (pos,
+    abundance), those of hit h at vertices[h.first:h.first + h.n_pos]."""
+    import numpy as np
+
+    byte_off = np.ascontiguousarray(byte_off, dtype=np.uint64)
+    lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+    if byte_off.shape != lengths.shape or byte_off.ndim != 1:
+        raise ValueError("byte_off and lengths are one-dimensional arrays of the same length")
+    n = len(lengths)
+    packed = np.ascontiguousarray(packed, dtype=np.uint8)
+    padded = np.concatenate((packed, np.zeros(16, dtype=np.uint8)))
+    rev = None
+    if reverse is not None:
+        rev = np.ascontiguousarray(np.asarray(reverse) != 0, dtype=np.uint8)
+        if rev.shape != lengths.shape:
+            raise ValueError("reverse has one entry per sequence")
+    seqs = capi.PagSeqs(n, byte_off.ctypes.data, lengths.ctypes.data, padded.ctypes.data, len(packed))
+    hit_off = np.zeros(n + 1, dtype=np.uint64)
+    n_hits, n_vert = C.c_uint64(), C.c_uint64()
+    handle = g if isinstance(g, C.c_void_p) else C.c_void_p(g)
+
+    def call(hits, hit_cap, vert, vert_cap):
+        return hip.pag_find_all_batch(handle, C.byref(seqs), None if rev is None else rev.ctypes.data, hit_off.ctypes.data, hits, hit_cap,
+                                      vert, vert_cap, C.byref(n_hits), C.byref(n_vert), None)
+
+    rc = call(None, 0, None, 0)
+    if rc not in (capi.PAG_OK, capi.PAG_ERANGE) or (rc == capi.PAG_ERANGE and n_hits.value == 0):
+        raise RuntimeError(f"pag_find_all_batch failed ({rc}): {hip.pag_last_error().decode()}")
+    hits = np.zeros(n_hits.value, dtype=capi.FIND_HIT_DTYPE)
+    vertices = np.zeros(n_vert.value, dtype=capi.FIND_VERTEX_DTYPE)
+    if n_hits.value:
+        rc = call(hits.ctypes.data, len(hits), vertices.ctypes.data if len(vertices) else None, len(vertices))
+        if rc != capi.PAG_OK:
+            raise RuntimeError(f"pag_find_all_batch failed ({rc}): {hip.pag_last_error().decode()}")
+    return hit_off, hits, vertices
+
+
 def pagraph_argv(binary, in_dir, out_dir, threads=1, epsilon=10, cov=2, min_len=50):
     """The argv AlignGraph2.py uses for pagraph (reference AlignGraph2.py:414-427), incl. the doubled -r."""
     return [binary, "-t", str(threads), "-r", "dummy", "-k", os.path.join(in_dir, "kmer.bin"),

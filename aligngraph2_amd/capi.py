@@ -150,6 +150,20 @@ class PagSuccQuery(C.Structure):
     _fields_ = [("code", _u32), ("reserved", _u32), ("pos", _u64)]
 
 
+class PagFindHit(C.Structure):
+    _c_name_ = "pag_find_hit"
+    _fields_ = [("offset", _u32), ("code", _u32), ("first", _u64), ("n_pos", _u32), ("reserved", _u32)]
+
+
+class PagFindVertex(C.Structure):
+    _c_name_ = "pag_find_vertex"
+    _fields_ = [("pos", _u64), ("abundance", _u32), ("reserved", _u32)]
+
+
+# ... as numpy record types (derived: the Structures above are what tests/test_abi.py holds to the header)
+FIND_HIT_DTYPE, FIND_VERTEX_DTYPE = np.dtype(PagFindHit), np.dtype(PagFindVertex)
+
+
 class CnsAln(C.Structure):
     _c_name_ = "pag_cns_aln"
     _fields_ = [("str_off", _u64), ("len", _u32), ("start", _u32), ("weight", _i32), ("reserved", _u32)]
@@ -200,7 +214,7 @@ class DebugWalkContig(C.Structure):
 
 
 STRUCTS = {s._c_name_: s for s in (PagSeqs, PagAlnDb, PagBuildInput, PagRawDb, PagRawInput, BuildStats, Csr, ShardSlice, Region,
-                                   SerialStats, TravelParams, TravelStats, PagSucc, PagSuccQuery, CnsAln, CnsPart, CnsSlice, CnsRow, KmerCountResult, TraverseStats,
+                                   SerialStats, TravelParams, TravelStats, PagSucc, PagSuccQuery, PagFindHit, PagFindVertex, CnsAln, CnsPart, CnsSlice, CnsRow, KmerCountResult, TraverseStats,
                                    DebugTravGraph, DebugWalkContig)}
 
 # structs of the headers that are deliberately mirrored neither in STRUCTS nor in DTYPES: C name -> why.  (The opaque
@@ -258,6 +272,8 @@ SIGNATURES = {
     "pag_successors": (_i64, [_vp, _u32, _u64, _vp, _u64]),
     "pag_successors_batch": (_int, [_vp, _vp, _u64, _u64, _f64, _vp, _vp, _vp, _u64, _u64p, _vp]),
     "pag_successors_batch_bytes": (_u64, [_u64, _u64]),
+    "pag_find_all_batch": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _u64p, _u64p, _vp]),
+    "pag_find_all_batch_bytes": (_u64, [_u64, _u64, _u64, _u64]),
     "pag_travel_path": (_vp, [_vp, _u64, _u64p]),
     "pag_travel_path_oriented": (_vp, [_vp, _u64, _int, _u64p]),
     "pag_reserve_walk_arena": (_int, [_vp, _u64]),

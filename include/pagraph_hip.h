@@ -461,6 +461,47 @@ typedef struct pag_succ_query {
 int pag_successors_batch(const pag_graph *g, const pag_succ_query *q, uint64_t n_q, uint64_t deviation, double error_rate,
                          uint64_t *off, int32_t *status, pag_succ *out, uint64_t cap, uint64_t *n_total, double *ms_kernels);
 uint64_t pag_successors_batch_bytes(uint64_t n_q, uint64_t n_records);
+/* Where pag_successors_batch's vertex names come from: PABruijnGraph::findAll (PABruijnGraph.cpp:339-353, through fromCode :90-96;
+ * find :334-337 is a sequence of k bases) for a LIST of sequences — the graph's vertices along a contig strand, a read, a single
+ * k-mer — from the same arrays of the FINISHED GRAPH (csrc/hip/k_find.hip, one wavefront per 1 024 offsets).  No view is needed,
+ * built or changed: pag_travel*, pag_successors* and pag_export_csr see the handle afterwards as they would without the call.  The
+ * walker's marks play no part: this is the reference's call on a fresh graph.
+ * All pointers are HOST memory.  seqs is 2-bit packed as pag_seqs says: anything but ACGT is already A, every sequence starts on a
+ * 4-byte boundary and ends inside packed_bytes, and packed ends with 16 readable bytes of padding.  reverse[i] != 0 searches the
+ * string CompressedSeq::toString(false) of sequence i (CompressedSeq.cpp:56-74: the complement read back to front), and offsets
+ * count in THAT string; reverse == NULL: all forward.  A sequence may be named more than once.
+ * hits[hit_off[i] .. hit_off[i + 1]) are the hits of sequence i in ascending offset: one for every offset 0 .. len - k whose
+ * k-mer is in the handle's solid set (a sequence shorter than k has none).  A solid k-mer nothing was placed on is a hit with
+ * n_pos = 0: the reference's table holds every solid k-mer.  A hit's vertices are its node's clustered positions in position order
+ * (the order sortKmerPosition leaves), each with its count; vert holds them in hit order, hits[h].first is the exclusive running
+ * sum of n_pos over the whole call (not per sequence).  (code, vert[].pos) is what pag_succ_query takes.
+ * *n_hits, *n_vert and hit_off[0 .. n_seqs] are complete whenever the lists were counted.  PAG_ERANGE, and nothing is written to
+ * hits or vert, when *n_hits > hit_cap or, with a vert buffer, *n_vert > vert_cap; both buffers may be NULL with cap 0: a sizing
+ * call.  vert == NULL with vert_cap == 0 and a sufficient hit_cap: the hits are written, first and n_pos included, and no vertex is
+ * copied.  n_seqs = 0: PAG_OK, hit_off[0] = 0.  PAG_EINVAL when the handle holds no finished graph, or a sequence's byte_off is no
+ * multiple of 4 or the sequence lies beyond packed_bytes; PAG_ERANGE when the handle holds one rank's region of a block
+ * (pag_shard_set_region); PAG_ENODEV without a gfx950 device.
+ * *ms_kernels (may be NULL): device time of the call's kernels from events — the lists are counted, the counts scanned, the
+ * lists filled; copies and allocations are not in it.  The call's temporary device memory is a plain allocation of its own, freed
+ * before it returns (no pool slot): at most pag_find_all_batch_bytes(n_seqs, packed_bytes, n_hits, n_vert) bytes for that many
+ * hits and vertices written, as long as no two sequences share bytes of packed (a sequence named again adds 44 bytes per 1 024 of
+ * its offsets). */
+typedef struct pag_find_hit {
+    uint32_t offset;   /* where the k-mer starts in the sequence AS SEARCHED (see reverse) */
+    uint32_t code;     /* the k-mer */
+    uint64_t first;    /* its vertices: vert[first .. first + n_pos) */
+    uint32_t n_pos;    /* clustered positions of the node; 0: a solid k-mer nothing was placed on */
+    uint32_t reserved; /* 0 */
+} pag_find_hit;
+typedef struct pag_find_vertex {
+    uint64_t pos;       /* contig coordinate << 32 | reference coordinate: pag_succ_query.pos */
+    uint32_t abundance; /* the position's count (PANode::getAbundance, u16 in the graph) */
+    uint32_t reserved;  /* 0 */
+} pag_find_vertex;
+int pag_find_all_batch(const pag_graph *g, const pag_seqs *seqs, const uint8_t *reverse, uint64_t *hit_off, pag_find_hit *hits,
+                       uint64_t hit_cap, pag_find_vertex *vert, uint64_t vert_cap, uint64_t *n_hits, uint64_t *n_vert,
+                       double *ms_kernels);
+uint64_t pag_find_all_batch_bytes(uint64_t n_seqs, uint64_t packed_bytes, uint64_t n_hits, uint64_t n_vert);
 const pag_path_node *pag_travel_path(const pag_graph *g, uint64_t ctg_index, uint64_t *len);
 const pag_path_node *pag_travel_path_oriented(const pag_graph *g, uint64_t ctg_index, int forward, uint64_t *len);
 /* Optional: have the device memory the walks of pag_travel take their job buffers from (one arena per handle, kept between

@@ -1,0 +1,153 @@
+"""PABruijnGraph::findAll as plain numpy over a golden's graph dump — the yardstick of pag_find_all_batch.
+
+The rule (reference PAGraph/src/tools/graph/PABruijnGraph.cpp:339-353, through fromCode :90-96): every offset 0 .. len - k of the
+searched string whose k-mer is in the solid set is a hit, with the node the dense table holds for it — a node without positions
+where nothing was placed on the k-mer.  The searched string of a reverse strand is CompressedSeq::toString(false)
+(CompressedSeq.cpp:56-74): the complement of the PACKED sequence read back to front, so what was no ACGT is A there and T here.
+A k-mer's code has its first base most significant (A 0, C 1, G 2, T 3).
+
+The node table comes from tests/golden/<case>/graph.txt.gz (oracle/ref_harness/graph_dump.cpp): per config block the k-mers
+`K code n_positions n_children` with their positions `P ctg ref count` in position order.  The dump skips nodes without positions.
+
+find_all returns (hit_off, hits, vertices) in the layout of the call (include/pagraph_hip.h)."""
+import ctypes as C
+import functools
+import gzip
+import os
+
+import numpy as np
+
+import goldens
+import pagctl  # (puts the repository root on the path)
+from aligngraph2_amd import capi
+
+HIT, VERTEX = capi.FIND_HIT_DTYPE, capi.FIND_VERTEX_DTYPE
+_BASE = np.zeros(256, dtype=np.uint8)
+for _i, _c in enumerate("ACGT"):
+    _BASE[ord(_c)] = _i
+
+
+def bases(seq):
+    """a base string as the packed form holds it: A 0, C 1, G 2, T 3, anything else A"""
+    return _BASE[np.frombuffer(seq.encode(), dtype=np.uint8)]
+
+
+def codes(seq, k, reverse=False):
+    """the k-mer codes at the offsets 0 .. len - k of the searched string: `seq` itself, or its complement read back to front"""
+    b = bases(seq).astype(np.uint64)
+    if reverse:
+        b = (np.uint64(3) - b)[::-1]
+    n = len(b) - k + 1
+    if n <= 0:
+        return np.zeros(0, dtype=np.uint32)
+    c = np.zeros(n, dtype=np.uint64)
+    for i in range(k):
+        c = c * np.uint64(4) + b[i:i + n]
+    return c.astype(np.uint32)
+
+
+def pack(seqs):
+    """(packed uint8 without padding, byte_off, lengths): 2 bits per base, base i of a sequence in bits 2 * (i & 3) of its byte
+    i >> 2, every sequence on the next 4-byte boundary"""
+    lengths = np.array([len(s) for s in seqs], dtype=np.uint32)
+    nbytes = [4 * ((len(s) + 15) // 16) for s in seqs]
+    byte_off = np.concatenate(([0], np.cumsum(nbytes)))[:len(seqs)].astype(np.uint64)
+    packed = np.zeros(int(sum(nbytes)), dtype=np.uint8)
+    for s, off in zip(seqs, byte_off):
+        pad = np.zeros(4 * ((len(s) + 3) // 4), dtype=np.uint8)
+        pad[:len(s)] = bases(s)
+        q = pad.reshape(-1, 4)
+        packed[int(off):int(off) + q.shape[0]] = q[:, 0] | (q[:, 1] << 2) | (q[:, 2] << 4) | (q[:, 3] << 6)
+    return packed, byte_off, lengths
+
+
+def solid_of_words(words, k):
+    """the solid set pag_create makes of a solid-set file's words (ALL of them, the header word included): those that are
+    k-mer codes, sorted"""
+    words = np.asarray(words, dtype=np.uint64)
+    return np.unique(words[words < np.uint64(4 ** k)]).astype(np.uint32)
+
+
+def solid_codes(inp):
+    """the solid codes a handle made by pagctl.hip_create(inp) holds: from the words the loaded input hands to pag_create"""
+    words = np.ctypeslib.as_array(C.cast(inp.kmer_words, C.POINTER(C.c_uint64)), shape=(inp.n_kmer_words,))
+    return solid_of_words(words, inp.k)
+
+
+def make_table(code, n_pos, pos, cnt):
+    """a node table: the k-mers in ascending code, pos_off[n + 1], pos (contig << 32 | reference) and cnt per position"""
+    code = np.asarray(code, dtype=np.int64)
+    n_pos = np.asarray(n_pos, dtype=np.int64)
+    off = np.concatenate(([0], np.cumsum(n_pos)))
+    order = np.argsort(code, kind="stable")
+    assert len(np.unique(code)) == len(code)
+    take = np.repeat(off[:-1][order], n_pos[order]) + (np.arange(int(n_pos.sum())) - np.repeat(np.cumsum(n_pos[order]) - n_pos[order], n_pos[order]))
+    return {"code": code[order], "pos_off": np.concatenate(([0], np.cumsum(n_pos[order]))), "pos": np.asarray(pos, dtype=np.uint64)[take],
+            "cnt": np.asarray(cnt, dtype=np.uint32)[take]}
+
+
+@functools.lru_cache(maxsize=None)
+def node_tables(name):
+    """per config block of a golden: make_table of its dump"""
+    blocks = []
+    for line in gzip.open(os.path.join(goldens.GOLDEN, name, "graph.txt.gz"), "rt"):
+        t = line[0]
+        if t == "S":
+            blocks.append({"code": [], "n_pos": [], "pos": [], "cnt": []})
+            b = blocks[-1]
+        elif t == "K":
+            b["code"].append(int(line.split()[1]))
+            b["n_pos"].append(0)
+        elif t == "P":
+            p = line.split()
+            b["pos"].append((int(p[1]) << 32) | int(p[2]))
+            b["cnt"].append(int(p[3]))
+            b["n_pos"][-1] += 1
+    return [make_table(b["code"], b["n_pos"], b["pos"], b["cnt"]) for b in blocks]
+
+
+def table_of_csr(csr):
+    """make_table of a pag_export_csr result (pagctl._run's "csr")"""
+    pos = (csr["pos_ctg"].astype(np.uint64) << np.uint64(32)) | csr["pos_ref"].astype(np.uint64)
+    return make_table(csr["node_code"], np.diff(csr["pos_off"].astype(np.int64)), pos, csr["pos_cnt"])
+
+
+def find_all(table, solid, k, seqs, reverse=None):
+    """findAll of every string of `seqs` (reverse[i]: in its reverse strand) against the node table and the sorted solid codes
+    (None: every k-mer is solid)"""
+    reverse = [False] * len(seqs) if reverse is None else reverse
+    hit_off, offs, cds = [0], [np.zeros(0, dtype=np.int64)], [np.zeros(0, dtype=np.uint32)]
+    for s, r in zip(seqs, reverse):
+        c = codes(s, k, bool(r))
+        if solid is None:
+            at = np.arange(len(c))
+        else:
+            i = np.minimum(np.searchsorted(solid, c), max(len(solid) - 1, 0))
+            at = np.flatnonzero(solid[i] == c) if len(solid) else np.zeros(0, dtype=np.int64)
+        offs.append(at)
+        cds.append(c[at])
+        hit_off.append(hit_off[-1] + len(at))
+    offset, code = np.concatenate(offs), np.concatenate(cds)
+    hits = np.zeros(len(code), dtype=HIT)
+    hits["offset"], hits["code"] = offset, code
+    n_nodes = len(table["code"])
+    at = np.minimum(np.searchsorted(table["code"], code.astype(np.int64)), max(n_nodes - 1, 0))
+    found = (table["code"][at] == code) if n_nodes else np.zeros(len(code), dtype=bool)
+    n_pos = np.where(found, (table["pos_off"][1:] - table["pos_off"][:-1])[at] if n_nodes else 0, 0).astype(np.int64)
+    first = np.cumsum(n_pos) - n_pos
+    hits["n_pos"], hits["first"] = n_pos, first
+    take = np.repeat(table["pos_off"][:-1][at] if n_nodes else n_pos, n_pos) + (np.arange(int(n_pos.sum())) - np.repeat(first, n_pos))
+    vertices = np.zeros(len(take), dtype=VERTEX)
+    vertices["pos"], vertices["abundance"] = table["pos"][take], table["cnt"][take]
+    return np.array(hit_off, dtype=np.uint64), hits, vertices
+
+
+def read_fasta(path):
+    """[(name, sequence)] of a FASTA file"""
+    out = []
+    for line in open(path):
+        if line.startswith(">"):
+            out.append([line[1:].split()[0], []])
+        elif line.strip():
+            out[-1][1].append(line.strip())
+    return [(n, "".join(p)) for n, p in out]
