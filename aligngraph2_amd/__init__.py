@@ -160,6 +160,44 @@ def find_all_batch(hip, g, packed, byte_off, lengths, reverse=None):
     return hit_off, hits, vertices
 
 
+def walk_straight_batch(hip, g, queries, frames, excl, ctg_len, deviation, error_rate):
+    """pag_walk_straight_batch (include/pagraph_hip.h) in the finished graph of handle `g` of the bound library `hip`: queries,
+    frames and excl are arrays of capi.WALK_QUERY_DTYPE, capi.WALK_FRAME_DTYPE and capi.SUCC_QUERY_DTYPE (or what numpy converts
+    to them), ctg_len the contigs' lengths.  A sizing call, then the real one.  Returns (node_off, nodes, alt_off, alts, status):
+    the path of query i at nodes[node_off[i]:node_off[i + 1]] (capi.WALK_NODE_DTYPE: code, step, pos, abundance), the chosen class
+    of a walk that ended at a branch at alts[alt_off[i]:alt_off[i + 1]] (capi.SUCC_DTYPE), status[i] one of capi.PAG_WALK_END /
+    BRANCH / LIMIT / LEAP, or capi.PAG_EINVAL where the graph holds no such vertex (an empty path)."""
+    import numpy as np
+
+    q = np.ascontiguousarray(queries, dtype=capi.WALK_QUERY_DTYPE)
+    fr = np.ascontiguousarray(frames, dtype=capi.WALK_FRAME_DTYPE)
+    ex = np.ascontiguousarray(excl, dtype=capi.SUCC_QUERY_DTYPE)
+    lens = np.ascontiguousarray(ctg_len, dtype=np.uint32)
+    if q.ndim != 1 or fr.ndim != 1 or ex.ndim != 1 or lens.ndim != 1:
+        raise ValueError("queries, frames, excl and ctg_len are one-dimensional arrays")
+    n = len(q)
+    node_off, alt_off = np.zeros(n + 1, dtype=np.uint64), np.zeros(n + 1, dtype=np.uint64)
+    status = np.zeros(n, dtype=np.int32)
+    n_nodes, n_alts = C.c_uint64(), C.c_uint64()
+    handle = g if isinstance(g, C.c_void_p) else C.c_void_p(g)
+
+    def call(nodes, node_cap, alts, alt_cap):
+        return hip.pag_walk_straight_batch(handle, q.ctypes.data, n, fr.ctypes.data, len(fr), ex.ctypes.data, len(ex), lens.ctypes.data, len(lens),
+                                           int(deviation), float(error_rate), node_off.ctypes.data, nodes, node_cap, alt_off.ctypes.data, alts, alt_cap,
+                                           status.ctypes.data, C.byref(n_nodes), C.byref(n_alts), None)
+
+    rc = call(None, 0, None, 0)
+    if rc not in (capi.PAG_OK, capi.PAG_ERANGE) or (rc == capi.PAG_ERANGE and n_nodes.value == 0):
+        raise RuntimeError(f"pag_walk_straight_batch failed ({rc}): {hip.pag_last_error().decode()}")
+    nodes = np.zeros(n_nodes.value, dtype=capi.WALK_NODE_DTYPE)
+    alts = np.zeros(n_alts.value, dtype=capi.SUCC_DTYPE)
+    if n_nodes.value:
+        rc = call(nodes.ctypes.data, len(nodes), alts.ctypes.data if len(alts) else None, len(alts))
+        if rc != capi.PAG_OK:
+            raise RuntimeError(f"pag_walk_straight_batch failed ({rc}): {hip.pag_last_error().decode()}")
+    return node_off, nodes, alt_off, alts, status
+
+
 def pagraph_argv(binary, in_dir, out_dir, threads=1, epsilon=10, cov=2, min_len=50):
     """The argv AlignGraph2.py uses for pagraph (reference AlignGraph2.py:414-427), incl. the doubled -r."""
     return [binary, "-t", str(threads), "-r", "dummy", "-k", os.path.join(in_dir, "kmer.bin"),

@@ -26,6 +26,7 @@ CONSTANTS = {
     "PAG_ORIENT_NONE": -1, "PAG_ORIENT_REVERSE": 0, "PAG_ORIENT_FORWARD": 1, "PAG_ORIENT_BOTH": 2,
     "PAG_TRAVEL_RENDER_DUMPS": 1, "PAG_TRAVEL_RENDER_SEQS": 2,
     "PAG_DEBUG_WALK_GUARD": 16,
+    "PAG_WALK_END": 0, "PAG_WALK_BRANCH": 1, "PAG_WALK_LIMIT": 2, "PAG_WALK_LEAP": 3, "PAG_WALK_LIMIT_MAX": 65536,
 }
 globals().update(CONSTANTS)
 
@@ -160,8 +161,26 @@ class PagFindVertex(C.Structure):
     _fields_ = [("pos", _u64), ("abundance", _u32), ("reserved", _u32)]
 
 
+class PagWalkFrame(C.Structure):
+    _c_name_ = "pag_walk_frame"
+    _fields_ = [("ctg_left", _u32), ("ctg_right", _u32), ("rev_left", _u32), ("rev_right", _u32), ("split_size", _u64), ("leap_min", _f64),
+                ("hull_lo", _u32 * 2), ("hull_hi", _u32 * 2), ("excl_off", _u64), ("excl_n", _u64)]
+
+
+class PagWalkQuery(C.Structure):
+    _c_name_ = "pag_walk_query"
+    _fields_ = [("code", _u32), ("dist", _u32), ("pos", _u64), ("has_size", _u64), ("frame", _u32), ("limit", _u32)]
+
+
+class PagWalkNode(C.Structure):
+    _c_name_ = "pag_walk_node"
+    _fields_ = [("code", _u32), ("step", _u32), ("pos", _u64), ("abundance", _u32), ("reserved", _u32)]
+
+
 # ... as numpy record types (derived: the Structures above are what tests/test_abi.py holds to the header)
 FIND_HIT_DTYPE, FIND_VERTEX_DTYPE = np.dtype(PagFindHit), np.dtype(PagFindVertex)
+SUCC_DTYPE, SUCC_QUERY_DTYPE = np.dtype(PagSucc), np.dtype(PagSuccQuery)
+WALK_FRAME_DTYPE, WALK_QUERY_DTYPE, WALK_NODE_DTYPE = np.dtype(PagWalkFrame), np.dtype(PagWalkQuery), np.dtype(PagWalkNode)
 
 
 class CnsAln(C.Structure):
@@ -214,7 +233,7 @@ class DebugWalkContig(C.Structure):
 
 
 STRUCTS = {s._c_name_: s for s in (PagSeqs, PagAlnDb, PagBuildInput, PagRawDb, PagRawInput, BuildStats, Csr, ShardSlice, Region,
-                                   SerialStats, TravelParams, TravelStats, PagSucc, PagSuccQuery, PagFindHit, PagFindVertex, CnsAln, CnsPart, CnsSlice, CnsRow, KmerCountResult, TraverseStats,
+                                   SerialStats, TravelParams, TravelStats, PagSucc, PagSuccQuery, PagFindHit, PagFindVertex, PagWalkFrame, PagWalkQuery, PagWalkNode, CnsAln, CnsPart, CnsSlice, CnsRow, KmerCountResult, TraverseStats,
                                    DebugTravGraph, DebugWalkContig)}
 
 # structs of the headers that are deliberately mirrored neither in STRUCTS nor in DTYPES: C name -> why.  (The opaque
@@ -274,6 +293,9 @@ SIGNATURES = {
     "pag_successors_batch_bytes": (_u64, [_u64, _u64]),
     "pag_find_all_batch": (_int, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _u64p, _u64p, _vp]),
     "pag_find_all_batch_bytes": (_u64, [_u64, _u64, _u64, _u64]),
+    "pag_walk_straight_batch": (_int, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _u64, _u64, _f64, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _u64p, _u64p,
+                                       _vp]),
+    "pag_walk_straight_batch_bytes": (_u64, [_u64, _u64, _u64, _u64, _u64]),
     "pag_travel_path": (_vp, [_vp, _u64, _u64p]),
     "pag_travel_path_oriented": (_vp, [_vp, _u64, _int, _u64p]),
     "pag_reserve_walk_arena": (_int, [_vp, _u64]),

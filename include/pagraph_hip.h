@@ -502,6 +502,69 @@ int pag_find_all_batch(const pag_graph *g, const pag_seqs *seqs, const uint8_t *
                        uint64_t hit_cap, pag_find_vertex *vert, uint64_t vert_cap, uint64_t *n_hits, uint64_t *n_vert,
                        double *ms_kernels);
 uint64_t pag_find_all_batch_bytes(uint64_t n_seqs, uint64_t packed_bytes, uint64_t n_hits, uint64_t n_vert);
+/* Moving through the FINISHED GRAPH from the vertices the two calls above name: PAlgorithm::walkStraight (PAlgorithm.tcc:93-170, with
+ * classifySuccessors :35-90) for a LIST of start vertices — follow the graph while exactly one successor survives the filters, and
+ * say why the walk stopped (csrc/hip/k_walk_query.hip, one wavefront per query; every list is evaluated on demand as
+ * pag_successors_batch evaluates it, with the caller's deviation and error rate).  graphTravel (:172-298) is a host loop over this
+ * call.  No view is needed, built or changed: pag_travel*, pag_successors* and pag_export_csr see the handle
+ * afterwards as they would without the call.  The walker's marks play no part.
+ * All pointers are HOST memory.  q[i] is one walkStraight call: startNode (code, pos as pag_succ_query; dist = startNode.second),
+ * hasSize, limitation, and the frame — what walkStraight's caller fixes for a group of walks: ctgRange, the split and its
+ * parentFilter, here as data: the other strand's range, the caller's two ctgPosTables as hulls, its unique tables as the slice
+ * excl[excl_off .. + excl_n) of vertices, ascending by (code, pos) without duplicates (frames may share a slice).  ctg_len are
+ * the lengths PositionMapper is built from (the landing rule, singleToDual(tc).second > size * leap_min; the size past the table
+ * reads as 0).  A successor record (target t with contig coordinate tc, step, grade, ctg_similar) of the current vertex is kept when
+ *   t is not in the frame's excl slice;  tc == 0 or tc outside [rev_left, rev_right);
+ *   tc == 0, or ctg_similar, or tc outside [hull_lo[j], hull_hi[j]] for j = 0, 1 and outside the hull of the path's own coordinates;
+ *   t is not on the path;
+ *   it does not leap (tc != 0 and outside [ctg_left, ctg_right)), or has_size + the steps so far (dist included) >= split_size and
+ *   the landing is not refused.
+ * A leap or Amazing is class 0, Excellent 1, Good 2, Skip 3 (only once has_size + steps >= split_size); the first non-empty
+ * class decides: empty — PAG_WALK_END; two or more records — PAG_WALK_BRANCH; one — it is appended; if it leaps — PAG_WALK_LEAP;
+ * else if the path has `limit` entries — PAG_WALK_LIMIT.  A start whose contig coordinate leaps is a path of one entry, PAG_WALK_LEAP.
+ * nodes[node_off[i] .. node_off[i + 1]) is the path of q[i] in query order (a query named twice is answered twice): entry 0 the start
+ * with step = dist, every later entry with the edge step that led to it; abundance is the position's count (PANode::getAbundance).
+ * alts[alt_off[i] .. alt_off[i + 1]) is, for PAG_WALK_BRANCH, the class chosen at the last vertex in record order (two or more
+ * records, as pag_succ) and empty otherwise.  A q[i] that names no vertex has an empty path and status[i] = PAG_EINVAL (status may
+ * be NULL) and does not fail the call.
+ * *n_nodes, *n_alts, node_off[0 .. n_q] and alt_off[0 .. n_q] are complete whenever the walks were counted.  PAG_ERANGE, and nothing
+ * is written to nodes or alts, when *n_nodes > node_cap or *n_alts > alt_cap; both may be NULL with cap 0: a sizing call.  n_q = 0:
+ * PAG_OK.  PAG_EINVAL, before a device is touched, when the handle holds no finished graph, a query's frame is not below n_frames,
+ * a limit lies outside 2 .. PAG_WALK_LIMIT_MAX, or a frame's excl slice ends beyond n_excl or is not strictly ascending; PAG_ERANGE
+ * when the handle holds one rank's region of a block (pag_shard_set_region); PAG_ENODEV without a gfx950 device.
+ * *ms_kernels (may be NULL): device time of the call's kernels from events — the walks are counted, the counts scanned, the paths
+ * filled; copies and allocations are not in it.  The call's temporary device memory is a plain allocation of its own, freed before
+ * it returns (no pool slot): at most pag_walk_straight_batch_bytes(n_q, n_frames, n_excl, n_nodes, n_alts) bytes for that many
+ * entries written, and 16 bytes per contig of ctg_len. */
+#define PAG_WALK_END 0     /* no successor survived */
+#define PAG_WALK_BRANCH 1  /* more than one did: alts holds them */
+#define PAG_WALK_LIMIT 2   /* the path has `limit` entries */
+#define PAG_WALK_LEAP 3    /* the last entry lies outside [ctg_left, ctg_right) */
+#define PAG_WALK_LIMIT_MAX 65536
+typedef struct pag_walk_frame {
+    uint32_t ctg_left, ctg_right;    /* ctgRange: [dualToSingle(chosen, 0), dualToSingle(chosen, len)) */
+    uint32_t rev_left, rev_right;    /* the other strand of the same contig: successors with a contig coordinate in it are refused; 0,0: none */
+    uint64_t split_size;             /* splitSize */
+    double leap_min;                 /* splitMin */
+    uint32_t hull_lo[2], hull_hi[2]; /* the caller's ctgPosTables (travelSequence's global one, graphTravel's travel one); empty: lo = 0xFFFFFFFF, hi = 0 */
+    uint64_t excl_off, excl_n;       /* the caller's unique tables: excl[excl_off .. + excl_n) */
+} pag_walk_frame;
+typedef struct pag_walk_query {
+    uint32_t code, dist;             /* startNode: the vertex's k-mer and startNode.second (k for a seed, the edge step for an alternative) */
+    uint64_t pos;                    /* contig coordinate << 32 | reference coordinate, as pag_succ_query */
+    uint64_t has_size;               /* walkStraight's hasSize */
+    uint32_t frame, limit;           /* index into frames; limitation, 2 .. PAG_WALK_LIMIT_MAX */
+} pag_walk_query;
+typedef struct pag_walk_node {
+    uint32_t code, step;
+    uint64_t pos;
+    uint32_t abundance, reserved;
+} pag_walk_node;
+int pag_walk_straight_batch(const pag_graph *g, const pag_walk_query *q, uint64_t n_q, const pag_walk_frame *frames, uint64_t n_frames,
+                            const pag_succ_query *excl, uint64_t n_excl, const uint32_t *ctg_len, uint64_t n_ctgs, uint64_t deviation,
+                            double error_rate, uint64_t *node_off, pag_walk_node *nodes, uint64_t node_cap, uint64_t *alt_off, pag_succ *alts,
+                            uint64_t alt_cap, int32_t *status, uint64_t *n_nodes, uint64_t *n_alts, double *ms_kernels);
+uint64_t pag_walk_straight_batch_bytes(uint64_t n_q, uint64_t n_frames, uint64_t n_excl, uint64_t n_nodes, uint64_t n_alts);
 const pag_path_node *pag_travel_path(const pag_graph *g, uint64_t ctg_index, uint64_t *len);
 const pag_path_node *pag_travel_path_oriented(const pag_graph *g, uint64_t ctg_index, int forward, uint64_t *len);
 /* Optional: have the device memory the walks of pag_travel take their job buffers from (one arena per handle, kept between
