@@ -1,6 +1,7 @@
 // Kernel-level check of K3/K4 (cluster_short/long, edges_short/long) against a sequential restatement of
 // KMerAdjNode::cluster / removeDuplicate on segmented streams.  Test infrastructure (GPU only).
-//   seg_kernels_test [n_segments] [seed] [wide] [eps]     random segment lengths (eps: default 10)
+//   seg_kernels_test [n_segments] [seed] [wide] [eps] [whole]     random segment lengths (eps: default 10; whole: coordinates drawn
+//                                                                 from the whole 32-bit range)
 //   seg_kernels_test case <name> <wide> [eps | all]       one constructed case (see build_case); "all" = every eps of EPS_ALL
 //   seg_kernels_test describe <name> <wide>               the shape of a case's segments, from the sequential scan (no device)
 //   seg_kernels_test list                                 the names of the constructed cases
@@ -233,7 +234,9 @@ static int check_stream(const char *label, const Stream &st, uint32_t eps, bool 
 }
 
 // ---------------------------------------------------------------------------------------- random segment lengths
-static void random_stream(Stream &st, uint64_t n_seg_target, unsigned seed) {
+// whole: the centres of a segment's positions are drawn from the whole 32-bit range instead of a few thousand coordinates (every
+// eighth segment around 2^31, its jitter across the top bit), and the spread segments' positions likewise
+static void random_stream(Stream &st, uint64_t n_seg_target, unsigned seed, bool whole = false) {
     std::mt19937_64 rng(seed);
     std::vector<uint32_t> &key = st.key;
     std::vector<uint64_t> &val = st.val, &eval = st.eval;
@@ -260,6 +263,12 @@ static void random_stream(Stream &st, uint64_t n_seg_target, unsigned seed) {
                 c0[c] = top ? 0xFFFFFFFFu - 14u - (uint32_t)(rng() % 30) : 1u + (uint32_t)(rng() % 12);
                 r0[c] = rng() % 2 ? 0xFFFFFFFFu - 14u - (uint32_t)(rng() % 30) : 1u + (uint32_t)(rng() % 12);
             }
+        if (whole && sgi % 40 != 7)
+            for (int c = 0; c < 4; ++c) {
+                const bool at_top_bit = sgi % 8 == 3;
+                c0[c] = at_top_bit ? 0x80000000u - 7u - (uint32_t)(rng() % 8) : 1u + (uint32_t)(rng() % 0xFFFFFFF0ull);
+                r0[c] = at_top_bit ? 0x80000000u - 7u - (uint32_t)(rng() % 8) : 1u + (uint32_t)(rng() % 0xFFFFFFF0ull);
+            }
         for (uint32_t j = 0; j < len; ++j) {
             uint32_t c = (uint32_t)(rng() % centers);
             bool pass2 = j >= len / 2;
@@ -268,6 +277,10 @@ static void random_stream(Stream &st, uint64_t n_seg_target, unsigned seed) {
             if (spread) {
                 ctg = pass2 ? 0 : 1000 + (uint32_t)(rng() % 40000);
                 ref = 5000 + (uint32_t)(rng() % 40000);
+                if (whole) {
+                    ctg = pass2 ? 0 : 1u + (uint32_t)(rng() % 0xFFFFFFFEull);
+                    ref = 1u + (uint32_t)(rng() % 0xFFFFFFFEull);
+                }
             }
             key.push_back(code);
             val.push_back((uint64_t)ctg << 32 | ref);
@@ -588,12 +601,19 @@ int main(int argc, char **argv) {
     const unsigned seed = argc > 2 ? (unsigned)atoi(argv[2]) : 1;
     const bool wide = argc > 3 ? atoi(argv[3]) != 0 : false;  // (the short path with 64-record masks instead of 32)
     const uint32_t eps = argc > 4 ? (uint32_t)strtoul(argv[4], nullptr, 10) : 10u;
+    const bool whole = argc > 5 && strcmp(argv[5], "whole") == 0;
     Stream st;
-    random_stream(st, n_seg_target, seed);
+    random_stream(st, n_seg_target, seed, whole);
     const int bad = check_stream("random", st, eps, wide, true, true);
     if (bad < 0) return 2;
-    uint64_t n_seg = 0;
-    for (size_t i = 0; i < st.key.size(); ++i) n_seg += i == 0 || st.key[i] != st.key[i - 1];
-    printf("%s: %llu records, %llu segments, eps %u\n", bad ? "FAIL" : "OK", (unsigned long long)st.key.size(), (unsigned long long)n_seg, eps);
+    uint64_t n_seg = 0, n_top = 0, n_pos = 0;
+    for (size_t i = 0; i < st.key.size(); ++i) {
+        n_seg += i == 0 || st.key[i] != st.key[i - 1];
+        const uint32_t c = (uint32_t)(st.val[i] >> 32), r = (uint32_t)st.val[i];
+        n_top += (c >> 31) + (r >> 31);
+        n_pos += (c != 0) + (r != 0);
+    }
+    printf("%s: %llu records, %llu segments, eps %u, %llu of %llu coordinates with the top bit set\n", bad ? "FAIL" : "OK", (unsigned long long)st.key.size(),
+           (unsigned long long)n_seg, eps, (unsigned long long)n_top, (unsigned long long)n_pos);
     return bad ? 1 : 0;
 }

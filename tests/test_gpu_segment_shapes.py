@@ -105,6 +105,20 @@ def test_segment_kernels_random_mode_at_eps(eps, wide):
     assert r.returncode == 0 and f"eps {eps}" in r.stdout, r.stdout[-3000:] + r.stderr[-1000:]
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("wide", [0, 1])
+@pytest.mark.parametrize("eps", [0, 3000, (1 << 31) + 5])
+def test_segment_kernels_random_mode_over_the_whole_coordinate_range(eps, wide):
+    """The random mode draws its positions from [1000, 1315) x [5000, 5315), every 40th segment within 44 of either end of the 32-bit
+    range: bit 31 is set only next to 2^32.  `whole` draws the centres from the whole range, every eighth segment around 2^31 with
+    its jitter across the top bit: about half of the coordinates have the top bit set (the program counts them)."""
+    assert os.path.exists(SEG), "run `make harness`"
+    r = subprocess.run([SEG, "20000", "2", str(wide), str(eps), "whole"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and f"eps {eps}" in r.stdout, r.stdout[-3000:] + r.stderr[-1000:]
+    top, of = (int(x) for x in re.search(r"(\d+) of (\d+) coordinates with the top bit set", r.stdout).groups())
+    assert 0.3 * of < top < 0.7 * of, r.stdout[-300:]
+
+
 def _sort_check(*args):
     assert os.path.exists(SORT), "run `make harness`"
     r = subprocess.run([SORT, "check"] + [str(a) for a in args], capture_output=True, text=True, timeout=300)

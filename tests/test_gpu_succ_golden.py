@@ -64,6 +64,16 @@ def reference_blocks(name):
     return blocks
 
 
+def reference_of_rule(g, off, rec):
+    """a block of succ_rule.load_graph and the rule's lists of ALL its vertices (succ_rule.successors) in the form
+    check_against_reference takes: the vertices keyed by (code, ctg, ref) in the graph's own order"""
+    keys = list(zip(g["code"][g["node_of_vertex"]].tolist(), g["ctg"].tolist(), g["ref"].tolist()))
+    index = {key: i for i, key in enumerate(keys)}
+    assert len(index) == len(keys), "(code, position) does not name a vertex uniquely"
+    assert len(off) == len(keys) + 1 and off[-1] == len(rec)
+    return {"keys": keys, "index": index, "off": np.asarray(off, dtype=np.int64), "rec": np.asarray(rec, dtype=np.int64).reshape(-1, 4)}
+
+
 def block_orient(ind, block, ctg_names):
     """PAG_ORIENT_* per contig of the -c file for config block `block` (hip_backend.cpp orientations())"""
     lines = open(os.path.join(ind, "config.txt")).read().split("\n")

@@ -302,7 +302,46 @@ def test_commit_equals_the_rule(hip, in_lo, n_in):
 def test_pack_paths_equal_the_rule(hip, which):
     rng = np.random.default_rng(11)
     G = R.random_graph(rng, 900, [0] + list(range(1000, 1040)))
-    batch = R.pack_batches(rng, G)[which]
+    _pack_and_compare(hip, G, R.pack_batches(rng, G)[which], f"batch {which}")
+
+
+def test_pack_paths_across_2_31_and_a_log_at_its_clamp(hip):
+    """Path coordinates on both sides of 2^31 in one block, blocks all below and all above it: the block tables' highest / lowest /
+    lowest non-zero coordinate are unsigned maxima and minima.  And a leap job's log as walk_job writes it for such a path — the
+    lowest contig-following coordinate clamped to 2^31 - 1, "none" recorded as the same value: blocks whose boundaries are all at
+    the clamp, and blocks with one entry a little below it."""
+    rng = np.random.default_rng(12)
+    top = 1 << 31
+    G = R.random_graph(rng, 900, [0] + list(range(top - 20, top + 20)))
+    c_of = R.ctg_of(G["upos"])
+    below, above, free = np.flatnonzero((c_of != 0) & (c_of < top)), np.flatnonzero(c_of >= top), np.flatnonzero(c_of == 0)
+    assert min(len(below), len(above), len(free)) >= 64
+
+    def job(length, leap):
+        v = rng.integers(0, G["n_pos"], size=length).astype(np.uint32)
+        if length >= 256:
+            v[64:128], v[128:192] = rng.choice(below, size=64), rng.choice(above, size=64)
+            v[192:256] = rng.choice(np.concatenate([above, free]), size=64)
+        s = rng.integers(0, 1 << 24, size=length).astype(np.uint32)
+        if not leap:
+            return v, s, None
+        c = c_of[v]
+        # (the true value: none beside a coordinate-free vertex, a coordinate a little below the vertex's below 2^31, the vertex's own above)
+        elow = np.where(c == 0, 0xFFFFFFFF, np.where(c < top, np.maximum(c, 8) - rng.integers(0, 8, size=length), c))
+        x = (np.uint64(1) << np.uint64(63)) | (np.minimum(elow, 0x7FFFFFFF).astype(np.uint64) << np.uint64(32)) | rng.integers(0, 1 << 32, size=length, dtype=np.uint64)
+        x[rng.random(length) < 0.4] = 0  # (no boundary)
+        return v, s, x
+
+    batch = [job(63, True), job(300, False), job(300, True), job(65, True), job(1, True)]
+    w = R.pack_job(G, *batch[2])
+    agg, xagg = w[5 * 300:5 * 300 + 5 * 5].reshape(-1, 5).astype(np.int64), w[5 * 300 + 5 * 5:].reshape(-1, 2).astype(np.int64)
+    assert agg[1, 0] < top <= agg[2, 3] and agg[3, 2] == 0 and agg[3, 3] >= top, "no block all below / all above 2^31 / above with coordinate-free vertices"
+    assert ((agg[:, 0] >= top) & (agg[:, 3] < top)).any(), "no block whose coordinates lie on both sides of 2^31"
+    assert xagg[2, 0] == xagg[3, 0] == 0x7FFFFFFF and 0x7FFFFF00 < xagg[1, 0] < 0x7FFFFFFF, f"no block with every boundary at the clamp / one below it: {xagg[:, 0]}"
+    _pack_and_compare(hip, G, batch, "coordinates across 2^31")
+
+
+def _pack_and_compare(hip, G, batch, label):
     offs, total = R.pack_layout(batch)
     want = np.full(total, SENT, dtype=np.uint32)
     seq_v, seq_s, seq_x, rows, at = [], [], [], [], 0
@@ -334,7 +373,7 @@ def test_pack_paths_equal_the_rule(hip, which):
         rel -= 5 * nb
         return f"job {j} ({n} entries): leap table row {rel // 2}, word {rel % 2}" if rel < 2 * nb and leap else f"the untouched word behind job {j}"
 
-    _first_diff(f"batch {which}", "the packed words (arrays, block tables, and the untouched words between the jobs)", out, want, where)
+    _first_diff(label, "the packed words (arrays, block tables, and the untouched words between the jobs)", out, want, where)
 
 
 # =====================================================================================================================

@@ -150,10 +150,15 @@ class Constructed:
     """the graph of tests/walk_straight_cases.py in a handle (pag_shard_import; test_gpu_find.import_graph gives a graph one
     edge: this one needs its edges, and its counts in tcnt)"""
 
+    def __init__(self, L=None, ctg_len=cases.CTG_LEN, moved=None):
+        """L: the same graph's lists with its coordinates translated, ctg_len and moved (Case.frame_of) the layout and the frames
+        that go with them (tests/high_coords.py)"""
+        self.L, self.ids = (L, constructed()[1]) if L is not None else constructed()
+        self.ctg_len, self.moved = ctg_len, moved
+
     def __enter__(self):
         import torch
         self.hip = pagctl.hip_lib()
-        self.L, self.ids = constructed()
         g = self.L.g
         rng = np.random.default_rng(9)
         host = list(slice_arrays(g, rng))
@@ -179,10 +184,10 @@ class Constructed:
         return (int(self.vcode[v]), int(self.vpos[v]))
 
     def calls(self, picked=CASES):
-        return [(c.frame_of(self.ids), self.ids[c.start], c.dist, c.has_size, c.limit) for c in picked]
+        return [(c.frame_of(self.ids, self.moved), self.ids[c.start], c.dist, c.has_size, c.limit) for c in picked]
 
     def walk(self, q, frames, excl):
-        return ag.walk_straight_batch(self.hip, self.g, q, frames, excl, cases.CTG_LEN, cases.DEVIATION, cases.ERROR_RATE)
+        return ag.walk_straight_batch(self.hip, self.g, q, frames, excl, self.ctg_len, cases.DEVIATION, cases.ERROR_RATE)
 
     def __exit__(self, *exc):
         self.hip.pag_destroy(self.g)

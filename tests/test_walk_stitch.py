@@ -25,8 +25,10 @@ def _u32(a):
 
 
 def stitch(lib, T, parts, P, *, leap=False, log=None, max_back=0, max_chosen=1, max_probe=0, wd_below=0, wd_forced=0xFFFFFFFF, usable=True,
-           k=14, dev=20, split=10 ** 9, has_size=0):
-    """T, P: lists of (vertex, step, coordinate); parts: lengths of T's parts; log: per P entry (boundary?, elow, m0)"""
+           k=14, dev=20, split=10 ** 9, has_size=0, recorded=False):
+    """T, P: lists of (vertex, step, coordinate); parts: lengths of T's parts; log: per P entry (boundary?, elow, m0).
+    recorded: elow is the TRUE lowest coordinate (all ones: none) and the entry is written as walk_job's flush_log records it,
+    clamped to 31 bits"""
     tv, ts, tpc = (_u32([x[i] for x in T]) for i in range(3))
     pv, ps, ppc = (_u32([x[i] for x in P]) for i in range(3))
     off = np.concatenate([[0], np.cumsum(parts)]).astype(np.uint64)
@@ -34,7 +36,7 @@ def stitch(lib, T, parts, P, *, leap=False, log=None, max_back=0, max_chosen=1, 
     xl = xh = None
     if log is not None:
         xl = _u32([m0 for _, _, m0 in log])
-        xh = _u32([((1 << 31) | (elow & 0x7FFFFFFF)) if b else 0 for b, elow, _ in log])
+        xh = _u32([((1 << 31) | (min(elow, 0x7FFFFFFF) if recorded else elow & 0x7FFFFFFF)) if b else 0 for b, elow, _ in log])
     out = (C.c_uint64 * 6)()
     tail = np.zeros(len(P) + 1, dtype=np.uint32)
     lib.pagt_stitch.argtypes = [C.c_void_p] * 4 + [C.c_uint32] + [C.c_void_p] * 5 + [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32,
@@ -203,6 +205,37 @@ def test_try_merge_leap(lib, case, decision, why):
     if decision:
         be = [x[0] for x in P].index(T[-1][0])
         assert got[1] == len(P) - 1 - be and got[5] == [x[0] for x in P[be + 1:]]
+
+
+# The iteration log holds the lowest contig-following coordinate examined in 31 bits: flush_log (k5_travel.hip) records
+# min(elow, 0x7FFFFFFF), and "none" (all ones) is recorded as the same 0x7FFFFFFF.  Condition (4) refuses on elow <= dmax, dmax the
+# highest coordinate of D.  With the TRUE elow the decision would be "adopt iff elow > dmax"; with the recorded one it is "adopt
+# iff min(elow, 0x7FFFFFFF) > dmax": the same below 2^31 - 1, and a refusal for every dmax from 2^31 - 1 on, whatever the true
+# value — never an adoption the true value refuses.  Above 2^31 adoptions in the leaping zone stop ("Pieces").
+NONE = 0xFFFFFFFF
+
+
+@pytest.mark.parametrize("at", [16, 100], ids=["entry_read", "block_table"])
+@pytest.mark.parametrize("d", [-2, -1, 0, 1, 2])
+@pytest.mark.parametrize("elow", [0x7FFFFFFE, 0x7FFFFFFF, 0x80000000, NONE], ids=["2^31-2", "2^31-1", "2^31", "none"])
+def test_try_merge_leap_with_the_log_s_coordinate_at_its_clamp(lib, elow, d, at):
+    dmax = (0x7FFFFFFF if elow == NONE else elow) + d  # the highest coordinate of D: P[2], the last vertex before the common stretch
+    P = line(1000, 200, dmax - 6)                        # (the path crosses 2^31: the block tables' maxima and minima are unsigned)
+    T = line(100, 10, dmax - 50000) + P[3:13]            # T ends at P[12]; 9 common vertices behind the pair
+    assert max(c for _, _, c in T[:10] + P[:3]) == dmax and P[-1][2] < 2 ** 32
+    log = [(i % 4 == 0, NONE, NONE) for i in range(len(P))]  # boundaries every 4th vertex, one iteration behind the junction examined elow
+    log[at] = (True, elow, NONE)
+    got = stitch(lib, T, [10, 10], P, leap=True, log=log, recorded=True, k=14, dev=20, split=1000, has_size=5000)
+    unclamped = elow > dmax
+    assert not (got[0] == 1 and not unclamped), f"adopted where the true coordinate {elow:#x} refuses (dmax {dmax:#x})"
+    want = min(elow, 0x7FFFFFFF) > dmax
+    assert (got[0], got[2]) == ((1, -1) if want else (0, 6)), (hex(elow), hex(dmax), got[:3])
+    if unclamped and not want:
+        assert dmax >= 0x7FFFFFFF  # (the clamp's cost: a refusal the true value would not ask for, only from 2^31 - 1 on)
+    # the other conditions hold either way: with a log that examined nothing, below the clamp, the same junction is adopted
+    if dmax < 0x7FFFFFFF:
+        quiet = [(b, NONE, NONE) for b, _, _ in log]
+        assert stitch(lib, T, [10, 10], P, leap=True, log=quiet, recorded=True, k=14, dev=20, split=1000, has_size=5000)[0] == 1
 
 
 def test_chain_before_over_parts(lib):

@@ -65,11 +65,12 @@ class Case:
         self.name, self.start, self.path, self.status, self.alts = name, start, list(path), status, list(alts)
         self.dist, self.has_size, self.limit, self.frame = dist, has_size, limit, frame
 
-    def frame_of(self, ids):
+    def frame_of(self, ids, moved=None):
+        """moved: the frame's keyword arguments translated along the coordinate axis (tests/high_coords.py)"""
         kw = dict(ctg_left=1000, ctg_right=2000, rev_left=3000, rev_right=4000, split_size=NEVER, leap_min=1 - 0.9, ctg_len=CTG_LEN)
         kw.update(self.frame)
         kw["excl"] = [ids[v] for v in kw.get("excl", ())]
-        return Frame(**kw)
+        return Frame(**(moved(kw) if moved else kw))
 
 
 def build():
