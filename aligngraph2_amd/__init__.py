@@ -84,6 +84,23 @@ def load_host():
     return _host["lib"]
 
 
+def _sized_then_filled(hip, name, call, totals, dtypes):
+    """The two calls of a batch query `name` of the bound library `hip`: call(buf0, cap0, buf1, cap1, ...) with no room (the
+    sizing call; it leaves the counts in `totals`, ctypes integers, the first one the count without which nothing is filled),
+    then with numpy arrays of `dtypes` that hold them (an empty array goes as a null pointer).  Returns the arrays."""
+    import numpy as np
+
+    rc = call(*(None, 0) * len(totals))
+    if rc not in (capi.PAG_OK, capi.PAG_ERANGE) or (rc == capi.PAG_ERANGE and totals[0].value == 0):
+        raise RuntimeError(f"{name} failed ({rc}): {hip.pag_last_error().decode()}")
+    bufs = [np.zeros(t.value, dtype=d) for t, d in zip(totals, dtypes)]
+    if totals[0].value:
+        rc = call(*(x for b in bufs for x in (b.ctypes.data if len(b) else None, len(b))))
+        if rc != capi.PAG_OK:
+            raise RuntimeError(f"{name} failed ({rc}): {hip.pag_last_error().decode()}")
+    return bufs
+
+
 def successors_batch(hip, g, codes, pos, deviation, error_rate):
     """pag_successors_batch (include/pagraph_hip.h) for the vertices (codes[i], pos[i]) of the finished graph in handle `g` of
     the bound library `hip`: a sizing call, then the real one.  Returns (off, status, records): off[n + 1] uint64, status[n]
@@ -107,14 +124,7 @@ def successors_batch(hip, g, codes, pos, deviation, error_rate):
         return hip.pag_successors_batch(handle, q.ctypes.data, n, int(deviation), float(error_rate), off.ctypes.data, status.ctypes.data,
                                         out, cap, C.byref(total), None)
 
-    rc = call(None, 0)
-    if rc not in (capi.PAG_OK, capi.PAG_ERANGE) or (rc == capi.PAG_ERANGE and total.value == 0):
-        raise RuntimeError(f"pag_successors_batch failed ({rc}): {hip.pag_last_error().decode()}")
-    records = np.zeros(total.value, dtype=np.dtype(capi.PagSucc))
-    if total.value:
-        rc = call(records.ctypes.data, len(records))
-        if rc != capi.PAG_OK:
-            raise RuntimeError(f"pag_successors_batch failed ({rc}): {hip.pag_last_error().decode()}")
+    (records,) = _sized_then_filled(hip, "pag_successors_batch", call, (total,), (np.dtype(capi.PagSucc),))
     return off, status, records
 
 
@@ -148,15 +158,7 @@ def find_all_batch(hip, g, packed, byte_off, lengths, reverse=None):
         return hip.pag_find_all_batch(handle, C.byref(seqs), None if rev is None else rev.ctypes.data, hit_off.ctypes.data, hits, hit_cap,
                                       vert, vert_cap, C.byref(n_hits), C.byref(n_vert), None)
 
-    rc = call(None, 0, None, 0)
-    if rc not in (capi.PAG_OK, capi.PAG_ERANGE) or (rc == capi.PAG_ERANGE and n_hits.value == 0):
-        raise RuntimeError(f"pag_find_all_batch failed ({rc}): {hip.pag_last_error().decode()}")
-    hits = np.zeros(n_hits.value, dtype=capi.FIND_HIT_DTYPE)
-    vertices = np.zeros(n_vert.value, dtype=capi.FIND_VERTEX_DTYPE)
-    if n_hits.value:
-        rc = call(hits.ctypes.data, len(hits), vertices.ctypes.data if len(vertices) else None, len(vertices))
-        if rc != capi.PAG_OK:
-            raise RuntimeError(f"pag_find_all_batch failed ({rc}): {hip.pag_last_error().decode()}")
+    hits, vertices = _sized_then_filled(hip, "pag_find_all_batch", call, (n_hits, n_vert), (capi.FIND_HIT_DTYPE, capi.FIND_VERTEX_DTYPE))
     return hit_off, hits, vertices
 
 
@@ -186,15 +188,7 @@ def walk_straight_batch(hip, g, queries, frames, excl, ctg_len, deviation, error
                                            int(deviation), float(error_rate), node_off.ctypes.data, nodes, node_cap, alt_off.ctypes.data, alts, alt_cap,
                                            status.ctypes.data, C.byref(n_nodes), C.byref(n_alts), None)
 
-    rc = call(None, 0, None, 0)
-    if rc not in (capi.PAG_OK, capi.PAG_ERANGE) or (rc == capi.PAG_ERANGE and n_nodes.value == 0):
-        raise RuntimeError(f"pag_walk_straight_batch failed ({rc}): {hip.pag_last_error().decode()}")
-    nodes = np.zeros(n_nodes.value, dtype=capi.WALK_NODE_DTYPE)
-    alts = np.zeros(n_alts.value, dtype=capi.SUCC_DTYPE)
-    if n_nodes.value:
-        rc = call(nodes.ctypes.data, len(nodes), alts.ctypes.data if len(alts) else None, len(alts))
-        if rc != capi.PAG_OK:
-            raise RuntimeError(f"pag_walk_straight_batch failed ({rc}): {hip.pag_last_error().decode()}")
+    nodes, alts = _sized_then_filled(hip, "pag_walk_straight_batch", call, (n_nodes, n_alts), (capi.WALK_NODE_DTYPE, capi.SUCC_DTYPE))
     return node_off, nodes, alt_off, alts, status
 
 

@@ -15,7 +15,7 @@
 //   2. the solid test: one gather from the bitmap per offset, sixteen in flight per lane; a 16-bit mask per lane;
 //   3. the hits in offset order, 64 at a time: the exclusive sums of the lanes' hit counts say which lane holds hit h (six
 //      shuffles), its mask which of its offsets it is, its window (shuffles again) the code — no staging array;
-//   4. their nodes: lower bounds in tkey by groups of lanes (group_lower_bound, k_succ_query.hip's): with n hits in the turn
+//   4. their nodes: lower bounds in tkey by groups of lanes (group_heads, query_graph.hpp): with n hits in the turn
 //      the wave splits into groups of 64 / n lanes, each group its own search with that many pivots per round — a single k-mer
 //      (find): 64 pivots, five rounds over 10^8 slots; 33 and more: one lane each, a binary search; then tseg[head], one load;
 //   5. (fill) the hits to their places, then the (hit, position) pairs of the turn flattened in hit order, then position order,
@@ -23,14 +23,14 @@
 //      position cost the same per vertex.
 // The kernel runs twice: it counts hits and vertices per tile, the counts are scanned into tile bases (the vertex counts as two
 // 32-bit halves: a tile of a homopolymer can name one heavy node 1 024 times), it runs again and fills — the search is repeated,
-// nothing but twelve bytes per TILE is kept between the passes.  hit_off[], hits[] and vert[] are a function of the inputs alone.
+// nothing but twelve bytes per TILE is kept between the passes (the two passes of a call: query_call.hpp).  hit_off[], hits[] and
+// vert[] are a function of the inputs alone.
 // The walker's "used" marks play no part: this is the reference's call on a fresh graph.
 #include <algorithm>
-#include <cstring>
 
-#include "dev_call.hpp"
 #include "find_plan.hpp"
-#include "pag_graph_impl.hpp"
+#include "query_call.hpp"
+#include "query_graph.hpp"
 
 namespace pagdev {
 namespace {
@@ -57,11 +57,7 @@ struct FindArgs {
     const uint32_t *solid_bits;
     int all_solid;
     uint32_t k;
-    const uint32_t *tkey;
-    const uint64_t *tval;
-    const uint32_t *tseg;
-    const uint16_t *tcnt;
-    uint64_t T;
+    QueryGraph G;
     // count pass: per tile its hits and its vertices (low and high half)
     uint32_t *hcnt, *vlo, *vhi;
     // fill pass: the scans of the three, the buffers (vert null: hits only) and their sizes
@@ -71,53 +67,6 @@ struct FindArgs {
     FindVertex *vert;
     uint64_t n_vert;
 };
-
-// group_lower_bound of k_succ_query.hip (a copy: that file's code stays as it is).  The wave is cut into groups of G lanes (G a
-// power of two, the same in every lane; group = lane / G); every lane of a group passes the group's sorted array a[0 .. n), its
-// key, and whether the group searches at all.  Returns, in every lane of the group, the first index whose element is >= key (n:
-// none) and whether that element IS the key.  ALL 64 lanes call it together.
-struct Bound {
-    uint64_t at;
-    bool hit;
-};
-__device__ __forceinline__ Bound group_lower_bound(const uint32_t *__restrict__ a, uint64_t n, uint32_t key, uint32_t G, bool on) {
-    const uint32_t lane = lane_id(), sub = lane & (G - 1u);
-    const uint64_t gmask = (G == 64u ? ~0ull : (1ull << G) - 1ull) << (lane & ~(G - 1u));
-    uint64_t lo = 0, hi = on ? n : 0;
-    while (__ballot(hi - lo >= G) != 0ull) {
-        const bool act = hi - lo >= G;
-        const uint64_t chunk = (hi - lo + 1u + G) / (G + 1u);  // ceil((window + 1) / (G + 1))
-        const uint64_t p = lo + (uint64_t)(sub + 1u) * chunk - 1u;
-        const bool below = act && p < hi && a[p] < key;
-        const uint32_t c = (uint32_t)__popcll(__ballot(below) & gmask);  // (a[] is sorted: the group's first c lanes)
-        if (act) {
-            lo += (uint64_t)c * chunk;  // (behind pivot c - 1; c = 0: where it was)
-            hi = lo + chunk - 1u < hi ? lo + chunk - 1u : hi;  // (pivot c, which is not below the key — or the old end)
-        }
-    }
-    const uint64_t x = lo + sub;  // (the window holds at most G - 1 elements below hi)
-    const bool ok = on && x <= hi && x < n;
-    const uint32_t v = ok ? a[x] : 0u;
-    Bound r;
-    r.at = lo + (uint64_t)__popcll(__ballot(ok && x < hi && v < key) & gmask);
-    r.hit = (__ballot(ok && x == r.at && v == key) & gmask) != 0ull;
-    return r;
-}
-__device__ __forceinline__ uint32_t uniform_u32(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
-__device__ __forceinline__ uint32_t from_lane(uint32_t x, uint32_t l) { return (uint32_t)__shfl((int)x, (int)l); }
-__device__ __forceinline__ uint64_t from_lane(uint64_t x, uint32_t l) {
-    return (uint64_t)from_lane((uint32_t)x, l) | ((uint64_t)from_lane((uint32_t)(x >> 32), l) << 32);
-}
-// the last lane whose exclusive sum is <= x (the sums ascend with the lane): the lane that holds item x of the flattened lists,
-// when x is below their total
-template <typename T>
-__device__ __forceinline__ uint32_t holder_of(T excl, T x) {
-    uint32_t e = 0;
-#pragma unroll
-    for (uint32_t b = 32u; b != 0u; b >>= 1)
-        if (from_lane(excl, e + b) <= x) e += b;
-    return e;
-}
 
 // The window of a lane's sixteen offsets p0 .. p0 + 15 (K1's LaneWindow, k1_extract.hip): forward strand — the 64 bits from
 // base p0 on with their 2-bit groups reversed, a code is a shift and a mask; reverse strand — the 64 bits from the base the
@@ -202,18 +151,10 @@ __global__ void __launch_bounds__(256) k_find(FindArgs A) {
                 if (have && s < o_nth) m &= m - 1u;
             const uint32_t j = (uint32_t)__ffs((int)m) - 1u;  // (a lane that has a hit: the mask has more than o_nth bits)
             const uint32_t code = have ? ow.code(strand, kmask, j & 15u) : 0u;
-            // the hits' nodes, hit e by the lanes e W .. e W + W - 1
-            uint32_t W = 64u;
-            while (64u / W < turn) W >>= 1;
-            const uint32_t grp = lane / W;
-            const Bound nb = group_lower_bound(A.tkey, A.T, from_lane(code, grp), W, grp < turn);
-            const uint32_t mine = have ? lane * W : 0u;  // (first lane of the group that looked this lane's k-mer up)
-            const uint64_t head = from_lane(nb.at, mine);
-            const bool node = from_lane((uint32_t)nb.hit, mine) != 0u;
-            uint32_t n_pos = have && node ? A.tseg[head] : 0u;  // (none: a solid k-mer nothing was placed on)
-            if (n_pos > A.T - head) n_pos = (uint32_t)(A.T - head);  // (never in a finished graph: a segment ends inside the stream)
+            // the hits' nodes (absent: a solid k-mer nothing was placed on)
+            const Heads node = group_heads(A.G.tkey, A.G.T, A.G.tseg, code, turn);
             uint64_t n_pairs;
-            const uint64_t ex = wave_excl_sum64((uint64_t)n_pos, &n_pairs);
+            const uint64_t ex = wave_excl_sum64((uint64_t)node.count, &n_pairs);
             if (FILL) {
                 const uint64_t first = vb + tile_verts;
                 if (have && hb + h < A.n_hits) {
@@ -221,7 +162,7 @@ __global__ void __launch_bounds__(256) k_find(FindArgs A) {
                     r.offset = t0 + o * 16u + j;
                     r.code = code;
                     r.first = first + ex;
-                    r.n_pos = n_pos;
+                    r.n_pos = node.count;
                     r.reserved = 0u;
                     A.hits[hb + h] = r;
                 }
@@ -229,12 +170,12 @@ __global__ void __launch_bounds__(256) k_find(FindArgs A) {
                 for (uint64_t pb = 0; A.vert && pb < n_pairs; pb += 64u) {
                     const uint64_t x = pb + lane;
                     const uint32_t e = holder_of(ex, x);
-                    const uint64_t e_head = from_lane(head, e), e_ex = from_lane(ex, e);
+                    const uint64_t e_head = from_lane(node.head, e), e_ex = from_lane(ex, e);
                     if (x < n_pairs && first + x < A.n_vert) {
                         const uint64_t slot = e_head + (x - e_ex);
                         FindVertex v;
-                        v.pos = A.tval[slot];
-                        v.abundance = A.tcnt[slot];
+                        v.pos = A.G.tval[slot];
+                        v.abundance = A.G.tcnt[slot];
                         v.reserved = 0u;
                         A.vert[first + x] = v;
                     }
@@ -262,43 +203,17 @@ __global__ void k_find_offsets(const uint64_t *__restrict__ seq_tile, uint64_t n
     }
 }
 
-size_t align256(size_t x) { return (x + 255u) & ~(size_t)255u; }
-// the temporary device memory of a call: what is allocated before the counts are known
+// the temporary device memory of a call that is allocated before the counts are known
 struct FindLayout {
-    size_t packed, byte_off, len, seq_tile, tiles, hcnt, vlo, vhi, hbase, vlo_base, vhi_base, scan, hit_off, tot, bytes;
-    FindLayout(uint64_t n_seqs, uint64_t packed_bytes, uint64_t n_tiles) {
-        packed = 0;
-        byte_off = packed + align256(packed_bytes + 64);  // (the padding pag_seqs promises behind the last sequence, zeroed)
-        len = byte_off + align256(n_seqs * sizeof(uint64_t));
-        seq_tile = len + align256(n_seqs * sizeof(uint32_t));
-        tiles = seq_tile + align256((n_seqs + 1) * sizeof(uint64_t));
-        hcnt = tiles + align256(n_tiles * sizeof(FindTile));
-        vlo = hcnt + align256(n_tiles * sizeof(uint32_t));
-        vhi = vlo + align256(n_tiles * sizeof(uint32_t));
-        hbase = vhi + align256(n_tiles * sizeof(uint32_t));
-        vlo_base = hbase + align256((n_tiles + 1) * sizeof(uint64_t));
-        vhi_base = vlo_base + align256((n_tiles + 1) * sizeof(uint64_t));
-        scan = vhi_base + align256((n_tiles + 1) * sizeof(uint64_t));
-        hit_off = scan + align256(scan_tmp_bytes(n_tiles));
-        tot = hit_off + align256((n_seqs + 1) * sizeof(uint64_t));
-        bytes = tot + align256(2 * sizeof(uint64_t));
-    }
+    Carver c;
+    size_t packed, byte_off, len, seq_tile, tiles, hcnt, vlo, vhi, hbase, vlo_base, vhi_base, scan, hit_off, tot;
+    FindLayout(uint64_t n_seqs, uint64_t packed_bytes, uint64_t n_tiles)
+        : packed(c.take<uint8_t>(packed_bytes + 64)),  // (the padding pag_seqs promises behind the last sequence, zeroed)
+          byte_off(c.take<uint64_t>(n_seqs)), len(c.take<uint32_t>(n_seqs)), seq_tile(c.take<uint64_t>(n_seqs + 1)), tiles(c.take<FindTile>(n_tiles)),
+          hcnt(c.take<uint32_t>(n_tiles)), vlo(c.take<uint32_t>(n_tiles)), vhi(c.take<uint32_t>(n_tiles)), hbase(c.take<uint64_t>(n_tiles + 1)),
+          vlo_base(c.take<uint64_t>(n_tiles + 1)), vhi_base(c.take<uint64_t>(n_tiles + 1)), scan(c.take<char>(scan_tmp_bytes(n_tiles))),
+          hit_off(c.take<uint64_t>(n_seqs + 1)), tot(c.take<uint64_t>(2)) {}
 };
-
-struct FindScratch : DevCall {  // on the handle's stream; the events of the two timings
-    char *a = nullptr;
-    FindHit *hits = nullptr;
-    FindVertex *vert = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    FindScratch() : DevCall("pag_find_all_batch") {}
-    ~FindScratch() {
-        for (hipEvent_t e : ev)
-            if (e) hipEventDestroy(e);
-    }
-};
-
-// 4 waves per block, a wave per tile; more blocks than are resident at once: the dispatcher keeps every CU full to the end
-unsigned find_grid(uint64_t n_tiles) { return (unsigned)std::min<uint64_t>((n_tiles + 3) / 4, 256u * 32u); }
 
 }  // namespace
 }  // namespace pagdev
@@ -310,7 +225,7 @@ extern "C" {
 uint64_t pag_find_all_batch_bytes(uint64_t n_seqs, uint64_t packed_bytes, uint64_t n_hits, uint64_t n_vert) {
     if (!n_seqs) return 0;
     // (tiles: one per 1 024 offsets and a last one per sequence; sequences that share no byte of `packed` have 4 bases a byte at most)
-    return FindLayout(n_seqs, packed_bytes, n_seqs + packed_bytes / (FIND_TILE / 4)).bytes + n_hits * sizeof(pag_find_hit) + n_vert * sizeof(pag_find_vertex);
+    return FindLayout(n_seqs, packed_bytes, n_seqs + packed_bytes / (FIND_TILE / 4)).c.bytes + n_hits * sizeof(pag_find_hit) + n_vert * sizeof(pag_find_vertex);
 }
 
 int pag_find_all_batch(const pag_graph *g, const pag_seqs *seqs, const uint8_t *reverse, uint64_t *hit_off, pag_find_hit *hits, uint64_t hit_cap,
@@ -327,14 +242,8 @@ int pag_find_all_batch(const pag_graph *g, const pag_seqs *seqs, const uint8_t *
         set_error("pag_find_all_batch: the sequence list lacks byte_off, len or packed");
         return PAG_EINVAL;
     }
-    if (!g->tkey) {
-        set_error("pag_find_all_batch: the handle holds no finished graph (pag_process / pag_shard_import first)");
-        return PAG_EINVAL;
-    }
-    if (g->regional) {
-        set_error("pag_find_all_batch: the handle holds one rank's region of a block (pag_shard_set_region): a region does not hold every position of its k-mers");
-        return PAG_ERANGE;
-    }
+    int rc = check_finished_graph(g, "pag_find_all_batch", "position of its k-mers");
+    if (rc) return rc;
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || g->device >= n_dev) {
         (void)hipGetLastError();
@@ -358,80 +267,69 @@ int pag_find_all_batch(const pag_graph *g, const pag_seqs *seqs, const uint8_t *
         std::fill(hit_off, hit_off + n + 1, (uint64_t)0);
         return PAG_OK;
     }
-    FindScratch B;
-    const hipStream_t s = B.s = g->stream;
+    QueryCall B("pag_find_all_batch");
     const FindLayout L(n, seqs->packed_bytes, n_tiles);
-    int rc = B.open(g->device, false, DevCall::NO_STREAM);
-    if (rc || (rc = B.alloc(&B.a, L.bytes))) return rc;
-    for (hipEvent_t &ev : B.ev) PAG_HIP_TRY(hipEventCreate(&ev));
-    uint64_t *d_seq_tile = (uint64_t *)(B.a + L.seq_tile), *d_hbase = (uint64_t *)(B.a + L.hbase), *d_vlo_base = (uint64_t *)(B.a + L.vlo_base),
-             *d_vhi_base = (uint64_t *)(B.a + L.vhi_base), *d_hit_off = (uint64_t *)(B.a + L.hit_off), *d_tot = (uint64_t *)(B.a + L.tot);
+    if ((rc = B.open(g, L.c.bytes))) return rc;
+    const hipStream_t s = B.s;
+    uint64_t *d_seq_tile = B.at<uint64_t>(L.seq_tile), *d_hbase = B.at<uint64_t>(L.hbase), *d_vlo_base = B.at<uint64_t>(L.vlo_base),
+             *d_vhi_base = B.at<uint64_t>(L.vhi_base), *d_hit_off = B.at<uint64_t>(L.hit_off), *d_tot = B.at<uint64_t>(L.tot);
+    uint8_t *d_packed = B.at<uint8_t>(L.packed);
+    char *d_scan = B.at<char>(L.scan);
     FindArgs A{};
-    A.packed = (const uint8_t *)(B.a + L.packed);
-    A.byte_off = (const uint64_t *)(B.a + L.byte_off);
-    A.len = (const uint32_t *)(B.a + L.len);
-    A.tiles = (const FindTile *)(B.a + L.tiles);
+    A.packed = d_packed;
+    A.byte_off = B.at<uint64_t>(L.byte_off);
+    A.len = B.at<uint32_t>(L.len);
+    A.tiles = B.at<FindTile>(L.tiles);
     A.n_tiles = n_tiles;
     A.solid_bits = g->solid_bits;
     A.all_solid = g->all_solid;
     A.k = g->k;
-    A.tkey = g->tkey;
-    A.tval = g->tval;
-    A.tseg = g->tseg;
-    A.tcnt = g->tcnt;
-    A.T = g->n_t;
-    A.hcnt = (uint32_t *)(B.a + L.hcnt);
-    A.vlo = (uint32_t *)(B.a + L.vlo);
-    A.vhi = (uint32_t *)(B.a + L.vhi);
-    PAG_HIP_TRY(hipMemsetAsync(B.a + L.packed + seqs->packed_bytes, 0, 64, s));
-    if (seqs->packed_bytes) PAG_HIP_TRY(hipMemcpyAsync(B.a + L.packed, seqs->packed, seqs->packed_bytes, hipMemcpyHostToDevice, s));
-    PAG_HIP_TRY(hipMemcpyAsync(B.a + L.byte_off, seqs->byte_off, n * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-    PAG_HIP_TRY(hipMemcpyAsync(B.a + L.len, seqs->len, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    A.G = query_graph(g);
+    A.hcnt = B.at<uint32_t>(L.hcnt);
+    A.vlo = B.at<uint32_t>(L.vlo);
+    A.vhi = B.at<uint32_t>(L.vhi);
+    const dim3 grid(wave_per_item_grid(n_tiles));  // (a wave per tile)
+    PAG_HIP_TRY(hipMemsetAsync(d_packed + seqs->packed_bytes, 0, 64, s));
+    if (seqs->packed_bytes) PAG_HIP_TRY(hipMemcpyAsync(d_packed, seqs->packed, seqs->packed_bytes, hipMemcpyHostToDevice, s));
+    PAG_HIP_TRY(hipMemcpyAsync(B.at<uint64_t>(L.byte_off), seqs->byte_off, n * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    PAG_HIP_TRY(hipMemcpyAsync(B.at<uint32_t>(L.len), seqs->len, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     PAG_HIP_TRY(hipMemcpyAsync(d_seq_tile, plan.seq_tile.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-    PAG_HIP_TRY(hipMemcpyAsync(B.a + L.tiles, plan.tiles.data(), n_tiles * sizeof(FindTile), hipMemcpyHostToDevice, s));
-    PAG_HIP_TRY(hipEventRecord(B.ev[0], s));
-    k_find<false><<<dim3(find_grid(n_tiles)), dim3(256), 0, s>>>(A);
+    PAG_HIP_TRY(hipMemcpyAsync(B.at<FindTile>(L.tiles), plan.tiles.data(), n_tiles * sizeof(FindTile), hipMemcpyHostToDevice, s));
+    if ((rc = B.begin(QueryCall::COUNT))) return rc;
+    k_find<false><<<grid, dim3(256), 0, s>>>(A);
     PAG_HIP_TRY(hipGetLastError());
-    if ((rc = scan_u32_to_u64(A.hcnt, d_hbase, n_tiles, d_hbase + n_tiles, B.a + L.scan, s))) return rc;
-    if ((rc = scan_u32_to_u64(A.vlo, d_vlo_base, n_tiles, d_vlo_base + n_tiles, B.a + L.scan, s))) return rc;
-    if ((rc = scan_u32_to_u64(A.vhi, d_vhi_base, n_tiles, d_vhi_base + n_tiles, B.a + L.scan, s))) return rc;
+    if ((rc = scan_u32_to_u64(A.hcnt, d_hbase, n_tiles, d_hbase + n_tiles, d_scan, s))) return rc;
+    if ((rc = scan_u32_to_u64(A.vlo, d_vlo_base, n_tiles, d_vlo_base + n_tiles, d_scan, s))) return rc;
+    if ((rc = scan_u32_to_u64(A.vhi, d_vhi_base, n_tiles, d_vhi_base + n_tiles, d_scan, s))) return rc;
     k_find_offsets<<<dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, s>>>(d_seq_tile, n, n_tiles, d_hbase, d_vlo_base, d_vhi_base, d_hit_off, d_tot);
     PAG_HIP_TRY(hipGetLastError());
-    PAG_HIP_TRY(hipEventRecord(B.ev[1], s));
+    if ((rc = B.end(QueryCall::COUNT))) return rc;
     uint64_t tot[2] = {0, 0};
     PAG_HIP_TRY(hipMemcpyAsync(hit_off, d_hit_off, (n + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     PAG_HIP_TRY(hipMemcpyAsync(tot, d_tot, sizeof(tot), hipMemcpyDeviceToHost, s));
-    PAG_HIP_TRY(hipStreamSynchronize(s));
+    if ((rc = B.done(QueryCall::COUNT, ms_kernels))) return rc;
     *n_hits = tot[0];
     *n_vert = tot[1];
-    float ms = 0, ms2 = 0;
-    PAG_HIP_TRY(hipEventElapsedTime(&ms, B.ev[0], B.ev[1]));
-    if (ms_kernels) *ms_kernels = ms;
     if (tot[0] > hit_cap || (vert && tot[1] > vert_cap)) {
         set_error("pag_find_all_batch: %llu hits and %llu vertices, room for %llu and %llu", (unsigned long long)tot[0], (unsigned long long)tot[1],
                   (unsigned long long)hit_cap, (unsigned long long)vert_cap);
         return PAG_ERANGE;
     }
     if (tot[0] == 0) return PAG_OK;
-    if ((rc = B.alloc(&B.hits, tot[0]))) return rc;
-    if (vert && tot[1] && (rc = B.alloc(&B.vert, tot[1]))) return rc;
+    if ((rc = B.alloc(&A.hits, tot[0]))) return rc;
+    if (vert && tot[1] && (rc = B.alloc(&A.vert, tot[1]))) return rc;
     A.hbase = d_hbase;
     A.vlo_base = d_vlo_base;
     A.vhi_base = d_vhi_base;
-    A.hits = B.hits;
     A.n_hits = tot[0];
-    A.vert = B.vert;
-    A.n_vert = B.vert ? tot[1] : 0;
-    PAG_HIP_TRY(hipEventRecord(B.ev[2], s));
-    k_find<true><<<dim3(find_grid(n_tiles)), dim3(256), 0, s>>>(A);
+    A.n_vert = A.vert ? tot[1] : 0;
+    if ((rc = B.begin(QueryCall::FILL))) return rc;
+    k_find<true><<<grid, dim3(256), 0, s>>>(A);
     PAG_HIP_TRY(hipGetLastError());
-    PAG_HIP_TRY(hipEventRecord(B.ev[3], s));
-    PAG_HIP_TRY(hipMemcpyAsync(hits, B.hits, tot[0] * sizeof(pag_find_hit), hipMemcpyDeviceToHost, s));
-    if (B.vert) PAG_HIP_TRY(hipMemcpyAsync(vert, B.vert, tot[1] * sizeof(pag_find_vertex), hipMemcpyDeviceToHost, s));
-    PAG_HIP_TRY(hipStreamSynchronize(s));
-    PAG_HIP_TRY(hipEventElapsedTime(&ms2, B.ev[2], B.ev[3]));
-    if (ms_kernels) *ms_kernels = (double)ms + (double)ms2;
-    return PAG_OK;
+    if ((rc = B.end(QueryCall::FILL))) return rc;
+    PAG_HIP_TRY(hipMemcpyAsync(hits, A.hits, tot[0] * sizeof(pag_find_hit), hipMemcpyDeviceToHost, s));
+    if (A.vert) PAG_HIP_TRY(hipMemcpyAsync(vert, A.vert, tot[1] * sizeof(pag_find_vertex), hipMemcpyDeviceToHost, s));
+    return B.done(QueryCall::FILL, ms_kernels);
 }
 
 }  // extern "C"

@@ -6,7 +6,8 @@
 // reads, pag_api.hip): no traversal view, no compact CSR, no records of anybody else's vertex.
 //
 // One wavefront per query, every wave on its own (no block barrier, no LDS).  A query is a chain of dependent loads from
-// arrays of 10^8 entries, so the kernel is built to keep that chain short (group_lower_bound):
+// arrays of 10^8 entries, so the kernel is built to keep that chain short, with the toolbox of query_graph.hpp (steps 1 and 2
+// are this kernel's own, 3 and 4 are SuccPairs, which k_walk_query.hip deals from as well):
 //   1. the heads of the k-mer's tuple segment and of its edge segment, TOGETHER: lanes 0-31 search tkey, lanes 32-63 ekey, 32
 //      pivots per round each (six rounds over the 4.5e8 tuples of BASELINE configs[1]; one lane's binary search is 29);
 //   2. what stands at the two heads, requested together: the leader count tseg[head] and the first 64 leaders (one of them is
@@ -21,11 +22,11 @@
 //      whatever the error rate; a ballot and the count of the lower lanes give an accepted pair its place, so the list keeps
 //      the reference's order (PABruijnGraph.cpp:182-195).
 // The kernel runs twice: it counts, the counts are scanned into off[], it runs again and fills.  off[] and out[] are a function
-// of the inputs alone.  The walker's "used" marks play no part: this is the reference's call on a fresh graph.
+// of the inputs alone (the two passes of a call: query_call.hpp).  The walker's "used" marks play no part: this is the
+// reference's call on a fresh graph.
 #include <algorithm>
-#include <cstring>
 
-#include "dev_call.hpp"
+#include "query_call.hpp"
 #include "query_graph.hpp"
 
 namespace pagdev {
@@ -75,46 +76,21 @@ __global__ void __launch_bounds__(256) k_succ_query(QueryGraph G, const pag_succ
             const uint32_t ac = (uint32_t)(pos >> 32), ar = (uint32_t)pos;
             for (uint32_t eb = 0; found && eb < ne; eb += 64u) {
                 const uint32_t turn = ne - eb < 64u ? ne - eb : 64u;
-                if (eb != 0u) ev = lane < turn && eh + eb + lane < G.E ? G.eval[eh + eb + lane] : 0ull;
-                const uint32_t tcode = (uint32_t)(ev >> 32), step = (uint32_t)ev >> 1;
-                // head and leader count of every edge's target (none: a k-mer without positions), edge e by the lanes e W .. e W + W - 1
-                uint32_t W = 64u;
-                while (64u / W < turn) W >>= 1;
-                const uint32_t grp = lane / W;
-                const Bound tb = group_lower_bound(G.tkey, G.T, (uint32_t)__shfl((int)tcode, (int)grp), W, grp < turn);
-                const uint32_t mine = lane < turn ? lane * W : 0u;  // (first lane of the group that looked this lane's target up)
-                const uint64_t th = from_lane(tb.at, mine);
-                const bool t_hit = __shfl((int)tb.hit, (int)mine) != 0;
-                uint32_t tn = lane < turn && t_hit ? G.tseg[th] : 0u;
-                if (tn > G.T - th) tn = (uint32_t)(G.T - th);  // (never in a finished graph: a segment ends inside the stream)
-                // the candidate pairs of these edges, flattened: pair x belongs to the last edge whose prefix sum is <= x
-                uint64_t n_pairs;
-                const uint64_t ex = wave_excl_sum64((uint64_t)tn, &n_pairs);
-                for (uint64_t pb = 0; pb < n_pairs; pb += 64u) {
-                    const uint64_t x = pb + lane;
-                    uint32_t e = 0;
-#pragma unroll
-                    for (uint32_t b = 32u; b != 0u; b >>= 1) {
-                        const uint64_t v = __shfl(ex, (int)(e + b));
-                        if (v <= x) e += b;
-                    }
-                    const uint64_t e_th = __shfl(th, (int)e), e_ex = __shfl(ex, (int)e);
-                    const uint32_t e_step = (uint32_t)__shfl((int)step, (int)e), e_code = (uint32_t)__shfl((int)tcode, (int)e);
+                if (eb != 0u) ev = edge_turn(G, eh + eb, turn);  // (the first 64 came with the leaders)
+                const SuccPairs P(G, ev, turn);
+                for (uint64_t pb = 0; pb < P.n_pairs; pb += 64u) {
+                    const SuccPairs::Pair p = P.pair(pb + lane);
                     int grade = G_OOPS;
                     uint32_t esim = 0;
-                    uint64_t tp = 0;
-                    if (x < n_pairs) {
-                        tp = G.tval[e_th + (x - e_ex)];
-                        grade = d_check_position(ac, ar, (uint32_t)(tp >> 32), (uint32_t)tp, e_step, dev, err, &esim);
-                    }
+                    if (p.live) grade = d_check_position(ac, ar, (uint32_t)(p.pos >> 32), (uint32_t)p.pos, p.step, dev, err, &esim);
                     const uint64_t taken = __ballot(grade != G_OOPS);
                     if (FILL && grade != G_OOPS) {
                         const uint64_t slot = at + n_rec + (uint32_t)__popcll(taken & lanemask_lt());
                         if (slot < n_out) {
                             SuccOut r;
-                            r.code = e_code;
-                            r.step = e_step;
-                            r.pos = tp;
+                            r.code = p.code;
+                            r.step = p.step;
+                            r.pos = p.pos;
                             r.grade = (uint32_t)grade;
                             r.ctg_similar = esim & 1u;
                             out[slot] = r;
@@ -131,33 +107,14 @@ __global__ void __launch_bounds__(256) k_succ_query(QueryGraph G, const pag_succ
     }
 }
 
-size_t align256(size_t x) { return (x + 255u) & ~(size_t)255u; }
-// the temporary device memory of a call: what is allocated before the counts are known, and the records
+// the temporary device memory of a call that is allocated before the counts are known
 struct BatchLayout {
-    size_t q, off, cnt, status, scan, bytes;
-    explicit BatchLayout(uint64_t n_q) {
-        q = 0;
-        off = q + align256(n_q * sizeof(pag_succ_query));
-        cnt = off + align256((n_q + 1) * sizeof(uint64_t));
-        status = cnt + align256(n_q * sizeof(uint32_t));
-        scan = status + align256(n_q * sizeof(int32_t));
-        bytes = scan + align256(scan_tmp_bytes(n_q));
-    }
+    Carver c;
+    size_t q, off, cnt, status, scan;
+    explicit BatchLayout(uint64_t n_q)
+        : q(c.take<pag_succ_query>(n_q)), off(c.take<uint64_t>(n_q + 1)), cnt(c.take<uint32_t>(n_q)), status(c.take<int32_t>(n_q)),
+          scan(c.take<char>(scan_tmp_bytes(n_q))) {}
 };
-
-struct BatchScratch : DevCall {  // on the handle's stream; the events of the two timings
-    char *a = nullptr;
-    SuccOut *b = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    BatchScratch() : DevCall("pag_successors_batch") {}
-    ~BatchScratch() {
-        for (hipEvent_t e : ev)
-            if (e) hipEventDestroy(e);
-    }
-};
-
-// 4 waves per block; more blocks than are resident at once (6 or 7 per CU by the kernels' registers): the dispatcher keeps every CU full to the end
-unsigned query_grid(uint64_t n_q) { return (unsigned)std::min<uint64_t>((n_q + 3) / 4, 256u * 32u); }
 
 }  // namespace
 }  // namespace pagdev
@@ -167,65 +124,53 @@ using namespace pagdev;
 extern "C" {
 
 uint64_t pag_successors_batch_bytes(uint64_t n_q, uint64_t n_records) {
-    return n_q ? BatchLayout(n_q).bytes + n_records * sizeof(pag_succ) : 0;
+    return n_q ? BatchLayout(n_q).c.bytes + n_records * sizeof(pag_succ) : 0;
 }
 
 int pag_successors_batch(const pag_graph *g, const pag_succ_query *q, uint64_t n_q, uint64_t deviation, double error_rate, uint64_t *off,
                          int32_t *status, pag_succ *out, uint64_t cap, uint64_t *n_total, double *ms_kernels) {
     if (n_total) *n_total = 0;
     if (ms_kernels) *ms_kernels = 0;
-    if (!g || !off || !n_total || (!q && n_q) || (!out && cap)) return PAG_EINVAL;
-    if (!g->tkey) {
-        set_error("pag_successors_batch: the handle holds no finished graph (pag_process / pag_shard_import first)");
+    if (!g || !off || !n_total || (!q && n_q) || (!out && cap)) {
+        set_error("pag_successors_batch: a null handle, query list, off or total, or a null buffer with room");
         return PAG_EINVAL;
     }
-    if (g->regional) {
-        set_error("pag_successors_batch: the handle holds one rank's region of a block (pag_shard_set_region): a region does not hold every successor of its vertices");
-        return PAG_ERANGE;
-    }
+    int rc = check_finished_graph(g, "pag_successors_batch", "successor of its vertices");
+    if (rc) return rc;
     off[0] = 0;
     if (n_q == 0) return PAG_OK;
-    BatchScratch B;
-    const hipStream_t s = B.s = g->stream;
+    QueryCall B("pag_successors_batch");
     const BatchLayout L(n_q);
-    int rc = B.open(g->device, false, DevCall::NO_STREAM);
-    if (rc || (rc = B.alloc(&B.a, L.bytes))) return rc;
-    for (hipEvent_t &ev : B.ev) PAG_HIP_TRY(hipEventCreate(&ev));
-    pag_succ_query *d_q = (pag_succ_query *)(B.a + L.q);
-    uint64_t *d_off = (uint64_t *)(B.a + L.off);
-    uint32_t *d_cnt = (uint32_t *)(B.a + L.cnt);
-    int32_t *d_status = (int32_t *)(B.a + L.status);
-    QueryGraph G{g->tkey, g->tval, g->tseg, g->ekey, g->eval, g->eseg, g->n_t, g->n_e};
+    if ((rc = B.open(g, L.c.bytes))) return rc;
+    const hipStream_t s = B.s;
+    pag_succ_query *d_q = B.at<pag_succ_query>(L.q);
+    uint64_t *d_off = B.at<uint64_t>(L.off);
+    uint32_t *d_cnt = B.at<uint32_t>(L.cnt);
+    int32_t *d_status = B.at<int32_t>(L.status);
+    const QueryGraph G = query_graph(g);
     const uint32_t dev = (uint32_t)std::min<uint64_t>(deviation, 0xFFFFFFFFull);  // (coordinates are 32 bits: so is every difference of two)
+    const dim3 grid(wave_per_item_grid(n_q));
     PAG_HIP_TRY(hipMemcpyAsync(d_q, q, n_q * sizeof(pag_succ_query), hipMemcpyHostToDevice, s));
-    PAG_HIP_TRY(hipEventRecord(B.ev[0], s));
-    k_succ_query<false><<<dim3(query_grid(n_q)), dim3(256), 0, s>>>(G, d_q, n_q, dev, error_rate, d_cnt, d_status, nullptr, nullptr, 0);
+    if ((rc = B.begin(QueryCall::COUNT))) return rc;
+    k_succ_query<false><<<grid, dim3(256), 0, s>>>(G, d_q, n_q, dev, error_rate, d_cnt, d_status, nullptr, nullptr, 0);
     PAG_HIP_TRY(hipGetLastError());
-    if ((rc = scan_u32_to_u64(d_cnt, d_off, n_q, d_off + n_q, B.a + L.scan, s))) return rc;
-    PAG_HIP_TRY(hipEventRecord(B.ev[1], s));
+    if ((rc = scan_u32_to_u64(d_cnt, d_off, n_q, d_off + n_q, B.at<char>(L.scan), s)) || (rc = B.end(QueryCall::COUNT))) return rc;
     PAG_HIP_TRY(hipMemcpyAsync(off, d_off, (n_q + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     if (status) PAG_HIP_TRY(hipMemcpyAsync(status, d_status, n_q * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    PAG_HIP_TRY(hipStreamSynchronize(s));
-    const uint64_t total = off[n_q];
-    *n_total = total;
-    float ms = 0, ms2 = 0;
-    PAG_HIP_TRY(hipEventElapsedTime(&ms, B.ev[0], B.ev[1]));
-    if (ms_kernels) *ms_kernels = ms;
+    if ((rc = B.done(QueryCall::COUNT, ms_kernels))) return rc;
+    const uint64_t total = *n_total = off[n_q];
     if (total > cap) {
         set_error("pag_successors_batch: %llu records, room for %llu", (unsigned long long)total, (unsigned long long)cap);
         return PAG_ERANGE;
     }
     if (total == 0) return PAG_OK;
-    if ((rc = B.alloc(&B.b, total))) return rc;
-    PAG_HIP_TRY(hipEventRecord(B.ev[2], s));
-    k_succ_query<true><<<dim3(query_grid(n_q)), dim3(256), 0, s>>>(G, d_q, n_q, dev, error_rate, nullptr, nullptr, d_off, B.b, total);
+    SuccOut *d_out = nullptr;
+    if ((rc = B.alloc(&d_out, total)) || (rc = B.begin(QueryCall::FILL))) return rc;
+    k_succ_query<true><<<grid, dim3(256), 0, s>>>(G, d_q, n_q, dev, error_rate, nullptr, nullptr, d_off, d_out, total);
     PAG_HIP_TRY(hipGetLastError());
-    PAG_HIP_TRY(hipEventRecord(B.ev[3], s));
-    PAG_HIP_TRY(hipMemcpyAsync(out, B.b, total * sizeof(pag_succ), hipMemcpyDeviceToHost, s));
-    PAG_HIP_TRY(hipStreamSynchronize(s));
-    PAG_HIP_TRY(hipEventElapsedTime(&ms2, B.ev[2], B.ev[3]));
-    if (ms_kernels) *ms_kernels = (double)ms + (double)ms2;
-    return PAG_OK;
+    if ((rc = B.end(QueryCall::FILL))) return rc;
+    PAG_HIP_TRY(hipMemcpyAsync(out, d_out, total * sizeof(pag_succ), hipMemcpyDeviceToHost, s));
+    return B.done(QueryCall::FILL, ms_kernels);
 }
 
 }  // extern "C"

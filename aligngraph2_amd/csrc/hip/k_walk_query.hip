@@ -3,9 +3,9 @@
 // handle, as k_succ_query.hip reads them.  No traversal view, no successor records, no marks of the walker.
 //
 // One wavefront per query, every wave on its own (no block barrier, no LDS, nothing shared between workgroups).  A step of a walk:
-//   1. the successor list of the current vertex with k_succ_query.hip's machinery (query_graph.hpp): the head of the k-mer's edge
-//      segment (64 pivots per round), per 64 edges the heads of all targets at once by groups of lanes, the candidate pairs
-//      flattened and dealt to the lanes 64 at a time through d_check_position;
+//   1. the successor list of the current vertex with the toolbox of query_graph.hpp, as k_succ_query.hip: the head of the k-mer's
+//      edge segment (64 pivots per round), per 64 edges the candidate pairs (SuccPairs: the heads of all targets at once by groups
+//      of lanes, the pairs flattened) dealt to the lanes 64 at a time through d_check_position;
 //   2. instead of a record, every lane grades, filters and classifies its pair: the caller's frame (reverse strand, the two
 //      coordinate hulls), the walk's own hull, the leap test with the landing rule, the class by grade — all from registers and
 //      the contig table; then, ONLY for the pairs that are still alive, the two memberships: the frame's sorted `excl` slice (a
@@ -22,10 +22,9 @@
 // evaluates its last list once more to write the chosen class in record order.  Offsets and outputs are a function of the
 // inputs alone.
 #include <algorithm>
-#include <cstring>
 #include <vector>
 
-#include "dev_call.hpp"
+#include "query_call.hpp"
 #include "query_graph.hpp"
 
 namespace pagdev {
@@ -52,7 +51,6 @@ struct WalkTables {
     const pag_succ_query *excl;
     const uint64_t *starts, *sizes;  // PositionMapper's start table [n_ctgs + 1] (one entry, 0, without contigs) and the lengths
     uint32_t n_ctgs;
-    const uint16_t *tcnt;  // the positions' counts, by tuple slot
     uint32_t dev;
     double err;
 };
@@ -122,7 +120,7 @@ __global__ void __launch_bounds__(256) k_walk_query(QueryGraph G, WalkTables W, 
         if (found) {
             if (lane == 0u && cap > 0u) {
                 WalkNode r;
-                r.code = q_code, r.step = q_dist, r.pos = q_pos, r.abundance = W.tcnt[slot0], r.reserved = 0;
+                r.code = q_code, r.step = q_dist, r.pos = q_pos, r.abundance = G.tcnt[slot0], r.reserved = 0;
                 path[0] = r;
             }
             len = 1;
@@ -148,38 +146,13 @@ __global__ void __launch_bounds__(256) k_walk_query(QueryGraph G, WalkTables W, 
                 const uint32_t ne = __ballot(hd.hit) != 0ull ? G.eseg[eh] : 0u;
                 for (uint32_t eb = 0; eb < ne; eb += 64u) {
                     const uint32_t turn = ne - eb < 64u ? ne - eb : 64u;
-                    const uint64_t ev = lane < turn && eh + eb + lane < G.E ? G.eval[eh + eb + lane] : 0ull;
-                    const uint32_t tcode = (uint32_t)(ev >> 32), step = (uint32_t)ev >> 1;
-                    // head and leader count of every edge's target, edge e by the lanes e Wd .. e Wd + Wd - 1
-                    uint32_t Wd = 64u;
-                    while (64u / Wd < turn) Wd >>= 1;
-                    const uint32_t grp = lane / Wd;
-                    const Bound tb = group_lower_bound(G.tkey, G.T, (uint32_t)__shfl((int)tcode, (int)grp), Wd, grp < turn);
-                    const uint32_t mine = lane < turn ? lane * Wd : 0u;
-                    const uint64_t th = from_lane(tb.at, mine);
-                    const bool t_hit = __shfl((int)tb.hit, (int)mine) != 0;
-                    uint32_t tn = lane < turn && t_hit ? G.tseg[th] : 0u;
-                    if (tn > G.T - th) tn = (uint32_t)(G.T - th);  // (never in a finished graph: a segment ends inside the stream)
-                    uint64_t n_pairs;
-                    const uint64_t ex = wave_excl_sum64((uint64_t)tn, &n_pairs);
-                    for (uint64_t pb = 0; pb < n_pairs; pb += 64u) {
-                        const uint64_t x = pb + lane;
-                        uint32_t e = 0;
-#pragma unroll
-                        for (uint32_t b = 32u; b != 0u; b >>= 1) {
-                            const uint64_t v = __shfl(ex, (int)(e + b));
-                            if (v <= x) e += b;
-                        }
-                        const uint64_t e_th = __shfl(th, (int)e), e_ex = __shfl(ex, (int)e);
-                        const uint32_t e_step = (uint32_t)__shfl((int)step, (int)e), e_code = (uint32_t)__shfl((int)tcode, (int)e);
+                    const SuccPairs P(G, edge_turn(G, eh + eb, turn), turn);
+                    for (uint64_t pb = 0; pb < P.n_pairs; pb += 64u) {
+                        const SuccPairs::Pair p = P.pair(pb + lane);
+                        const uint64_t tp = p.pos;
                         int grade = G_OOPS;
                         uint32_t esim = 0;
-                        uint64_t tp = 0, slot = 0;
-                        if (x < n_pairs) {
-                            slot = e_th + (x - e_ex);
-                            tp = G.tval[slot];
-                            grade = d_check_position(ac, ar, (uint32_t)(tp >> 32), (uint32_t)tp, e_step, W.dev, W.err, &esim);
-                        }
+                        if (p.live) grade = d_check_position(ac, ar, (uint32_t)(tp >> 32), (uint32_t)tp, p.step, W.dev, W.err, &esim);
                         // the filters that cost nothing: the frame's reverse strand and hulls, the own hull, the leap test, the class
                         const uint32_t tc = (uint32_t)(tp >> 32);
                         const bool bound_by_hulls = tc != 0u && (esim & 1u) == 0u;
@@ -198,15 +171,15 @@ __global__ void __launch_bounds__(256) k_walk_query(QueryGraph G, WalkTables W, 
                             while (lo < hi) {
                                 const uint64_t mid = (lo + hi) >> 1;
                                 const uint32_t xc = X[mid].code;
-                                if (xc < e_code || (xc == e_code && X[mid].pos < tp)) lo = mid + 1u;
+                                if (xc < p.code || (xc == p.code && X[mid].pos < tp)) lo = mid + 1u;
                                 else hi = mid;
                             }
-                            if (lo < excl_n && X[lo].code == e_code && X[lo].pos == tp) ok = false;
+                            if (lo < excl_n && X[lo].code == p.code && X[lo].pos == tp) ok = false;
                         }
                         // ... and the path so far
                         for (uint64_t left = __ballot(ok); left != 0ull; left &= left - 1ull) {
                             const uint32_t l = (uint32_t)__ffsll((long long)left) - 1u;
-                            const uint32_t s_code = (uint32_t)__shfl((int)e_code, (int)l);
+                            const uint32_t s_code = (uint32_t)__shfl((int)p.code, (int)l);
                             const uint64_t s_pos = from_lane(tp, l);
                             bool on_path = false;
                             for (uint32_t jb = 0; jb < len && !on_path; jb += 64u) {
@@ -223,15 +196,15 @@ __global__ void __launch_bounds__(256) k_walk_query(QueryGraph G, WalkTables W, 
                             const uint32_t have = c == 0u ? c0 : c == 1u ? c1 : c == 2u ? c2 : c3;
                             if (have == 0u) {
                                 const uint32_t l = (uint32_t)__ffsll((long long)m) - 1u;
-                                const uint32_t f_code = (uint32_t)__shfl((int)e_code, (int)l), f_step = (uint32_t)__shfl((int)e_step, (int)l);
-                                const uint64_t f_pos = from_lane(tp, l), f_slot = from_lane(slot, l);
+                                const uint32_t f_code = (uint32_t)__shfl((int)p.code, (int)l), f_step = (uint32_t)__shfl((int)p.step, (int)l);
+                                const uint64_t f_pos = from_lane(tp, l), f_slot = from_lane(p.slot, l);
                                 if (lane == c) sv_code = f_code, sv_step = f_step, sv_pos = f_pos, sv_slot = f_slot;
                             }
                             if (FILL && emit == (int)c && ok && cls == c) {
                                 const uint64_t o = a_at + have + (uint32_t)__popcll(m & lanemask_lt());
                                 if (o < n_alts) {
                                     AltOut r;
-                                    r.code = e_code, r.step = e_step, r.pos = tp, r.grade = (uint32_t)grade, r.ctg_similar = esim & 1u;
+                                    r.code = p.code, r.step = p.step, r.pos = tp, r.grade = (uint32_t)grade, r.ctg_similar = esim & 1u;
                                     alts[o] = r;
                                 }
                             }
@@ -261,7 +234,7 @@ __global__ void __launch_bounds__(256) k_walk_query(QueryGraph G, WalkTables W, 
                 const uint64_t nx_pos = from_lane(sv_pos, c), nx_slot = from_lane(sv_slot, c);
                 if (lane == 0u && len < cap) {
                     WalkNode r;
-                    r.code = nx_code, r.step = nx_step, r.pos = nx_pos, r.abundance = W.tcnt[nx_slot], r.reserved = 0;
+                    r.code = nx_code, r.step = nx_step, r.pos = nx_pos, r.abundance = G.tcnt[nx_slot], r.reserved = 0;
                     path[len] = r;
                 }
                 ++len;
@@ -292,22 +265,14 @@ __global__ void __launch_bounds__(256) k_walk_query(QueryGraph G, WalkTables W, 
     }
 }
 
-size_t align256(size_t x) { return (x + 255u) & ~(size_t)255u; }
 // the temporary device memory of a call that is allocated before the counts are known
 struct WalkLayout {
-    size_t q, frames, excl, n_off, a_off, n_cnt, a_cnt, status, scan, bytes;
-    WalkLayout(uint64_t n_q, uint64_t n_frames, uint64_t n_excl) {
-        q = 0;
-        frames = q + align256(n_q * sizeof(pag_walk_query));
-        excl = frames + align256(n_frames * sizeof(pag_walk_frame));
-        n_off = excl + align256(n_excl * sizeof(pag_succ_query));
-        a_off = n_off + align256((n_q + 1) * sizeof(uint64_t));
-        n_cnt = a_off + align256((n_q + 1) * sizeof(uint64_t));
-        a_cnt = n_cnt + align256(n_q * sizeof(uint32_t));
-        status = a_cnt + align256(n_q * sizeof(uint32_t));
-        scan = status + align256(n_q * sizeof(int32_t));
-        bytes = scan + align256(scan_tmp_bytes(n_q));
-    }
+    Carver c;
+    size_t q, frames, excl, n_off, a_off, n_cnt, a_cnt, status, scan;
+    WalkLayout(uint64_t n_q, uint64_t n_frames, uint64_t n_excl)
+        : q(c.take<pag_walk_query>(n_q)), frames(c.take<pag_walk_frame>(n_frames)), excl(c.take<pag_succ_query>(n_excl)), n_off(c.take<uint64_t>(n_q + 1)),
+          a_off(c.take<uint64_t>(n_q + 1)), n_cnt(c.take<uint32_t>(n_q)), a_cnt(c.take<uint32_t>(n_q)), status(c.take<int32_t>(n_q)),
+          scan(c.take<char>(scan_tmp_bytes(n_q))) {}
 };
 // The counting run's path slots: one per wave of the grid, `stride` entries each (the largest limit of the call).  At most
 // SCRATCH_BYTES of them (but 64 waves at any limit), and never more waves than queries.
@@ -316,19 +281,6 @@ uint64_t grid_waves(uint64_t n_q, uint64_t stride) {
     const uint64_t fit = std::max<uint64_t>(GRID_WAVES_MIN, std::min<uint64_t>(GRID_WAVES_MAX, SCRATCH_BYTES / (stride * sizeof(WalkNode))));
     return (std::min<uint64_t>(n_q, fit) + 3u) / 4u * 4u;  // (whole blocks of 4 waves)
 }
-
-struct WalkScratch : DevCall {  // on the handle's stream; the events of the two timings
-    char *a = nullptr;
-    uint64_t *tables = nullptr;
-    WalkNode *paths = nullptr, *nodes = nullptr;
-    AltOut *alts = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    WalkScratch() : DevCall("pag_walk_straight_batch") {}
-    ~WalkScratch() {
-        for (hipEvent_t e : ev)
-            if (e) hipEventDestroy(e);
-    }
-};
 
 }  // namespace
 }  // namespace pagdev
@@ -339,7 +291,7 @@ extern "C" {
 
 uint64_t pag_walk_straight_batch_bytes(uint64_t n_q, uint64_t n_frames, uint64_t n_excl, uint64_t n_nodes, uint64_t n_alts) {
     if (n_q == 0) return 0;
-    return WalkLayout(n_q, n_frames, n_excl).bytes + grid_waves(n_q, PAG_WALK_LIMIT_MAX) * PAG_WALK_LIMIT_MAX * sizeof(pag_walk_node) +
+    return WalkLayout(n_q, n_frames, n_excl).c.bytes + grid_waves(n_q, PAG_WALK_LIMIT_MAX) * PAG_WALK_LIMIT_MAX * sizeof(pag_walk_node) +
            n_nodes * sizeof(pag_walk_node) + n_alts * sizeof(pag_succ);
 }
 
@@ -389,14 +341,8 @@ int pag_walk_straight_batch(const pag_graph *g, const pag_walk_query *q, uint64_
         set_error("pag_walk_straight_batch: a null handle");
         return PAG_EINVAL;
     }
-    if (!g->tkey) {
-        set_error("pag_walk_straight_batch: the handle holds no finished graph (pag_process / pag_shard_import first)");
-        return PAG_EINVAL;
-    }
-    if (g->regional) {
-        set_error("pag_walk_straight_batch: the handle holds one rank's region of a block (pag_shard_set_region): a region does not hold every successor of its vertices");
-        return PAG_ERANGE;
-    }
+    int rc = check_finished_graph(g, "pag_walk_straight_batch", "successor of its vertices");
+    if (rc) return rc;
     node_off[0] = alt_off[0] = 0;
     if (n_q == 0) return PAG_OK;
     // PositionMapper's tables over ctg_len (position_mapper.hpp:18-25); without contigs a single start, 0
@@ -408,62 +354,53 @@ int pag_walk_straight_batch(const pag_graph *g, const pag_walk_query *q, uint64_
         for (uint64_t c = 1; c < n_ctgs; ++c) starts[c] = starts[c - 1] + 3 * sizes[c - 1] + std::max(sizes[c - 1], sizes[c]);
         starts[n_ctgs] = starts[n_ctgs - 1] + 4 * sizes[n_ctgs - 1];
     }
-    WalkScratch B;
-    const hipStream_t s = B.s = g->stream;
+    QueryCall B("pag_walk_straight_batch");
     const WalkLayout L(n_q, n_frames, n_excl);
     const uint64_t waves = grid_waves(n_q, stride);
-    int rc = B.open(g->device, false, DevCall::NO_STREAM);
-    if (rc || (rc = B.alloc(&B.a, L.bytes)) || (rc = B.up(tables.data(), tables.size(), &B.tables, 0)) || (rc = B.alloc(&B.paths, waves * stride))) return rc;
-    for (hipEvent_t &ev : B.ev) PAG_HIP_TRY(hipEventCreate(&ev));
-    pag_walk_query *d_q = (pag_walk_query *)(B.a + L.q);
-    pag_walk_frame *d_frames = (pag_walk_frame *)(B.a + L.frames);
-    pag_succ_query *d_excl = (pag_succ_query *)(B.a + L.excl);
-    uint64_t *d_n_off = (uint64_t *)(B.a + L.n_off), *d_a_off = (uint64_t *)(B.a + L.a_off);
-    uint32_t *d_n_cnt = (uint32_t *)(B.a + L.n_cnt), *d_a_cnt = (uint32_t *)(B.a + L.a_cnt);
-    int32_t *d_status = (int32_t *)(B.a + L.status);
-    const QueryGraph G{g->tkey, g->tval, g->tseg, g->ekey, g->eval, g->eseg, g->n_t, g->n_e};
+    uint64_t *d_tables = nullptr;
+    WalkNode *d_paths = nullptr, *d_nodes = nullptr;
+    AltOut *d_alts = nullptr;
+    if ((rc = B.open(g, L.c.bytes)) || (rc = B.up(tables.data(), tables.size(), &d_tables, 0)) || (rc = B.alloc(&d_paths, waves * stride))) return rc;
+    const hipStream_t s = B.s;
+    pag_walk_query *d_q = B.at<pag_walk_query>(L.q);
+    pag_walk_frame *d_frames = B.at<pag_walk_frame>(L.frames);
+    pag_succ_query *d_excl = B.at<pag_succ_query>(L.excl);
+    uint64_t *d_n_off = B.at<uint64_t>(L.n_off), *d_a_off = B.at<uint64_t>(L.a_off);
+    uint32_t *d_n_cnt = B.at<uint32_t>(L.n_cnt), *d_a_cnt = B.at<uint32_t>(L.a_cnt);
+    int32_t *d_status = B.at<int32_t>(L.status);
+    const QueryGraph G = query_graph(g);
     WalkTables W;
-    W.frames = d_frames, W.excl = d_excl, W.starts = B.tables, W.sizes = B.tables + n_ctgs + 1, W.n_ctgs = (uint32_t)n_ctgs, W.tcnt = g->tcnt;
+    W.frames = d_frames, W.excl = d_excl, W.starts = d_tables, W.sizes = d_tables + n_ctgs + 1, W.n_ctgs = (uint32_t)n_ctgs;
     W.dev = (uint32_t)std::min<uint64_t>(deviation, 0xFFFFFFFFull);  // (coordinates are 32 bits: so is every difference of two)
     W.err = error_rate;
     PAG_HIP_TRY(hipMemcpyAsync(d_q, q, n_q * sizeof(pag_walk_query), hipMemcpyHostToDevice, s));
     PAG_HIP_TRY(hipMemcpyAsync(d_frames, frames, n_frames * sizeof(pag_walk_frame), hipMemcpyHostToDevice, s));
     if (n_excl) PAG_HIP_TRY(hipMemcpyAsync(d_excl, excl, n_excl * sizeof(pag_succ_query), hipMemcpyHostToDevice, s));
     const dim3 grid((unsigned)(waves / 4u));
-    PAG_HIP_TRY(hipEventRecord(B.ev[0], s));
-    k_walk_query<false><<<grid, dim3(256), 0, s>>>(G, W, d_q, n_q, d_n_cnt, d_a_cnt, d_status, nullptr, nullptr, nullptr, 0, nullptr, 0, B.paths, stride);
+    if ((rc = B.begin(QueryCall::COUNT))) return rc;
+    k_walk_query<false><<<grid, dim3(256), 0, s>>>(G, W, d_q, n_q, d_n_cnt, d_a_cnt, d_status, nullptr, nullptr, nullptr, 0, nullptr, 0, d_paths, stride);
     PAG_HIP_TRY(hipGetLastError());
-    if ((rc = scan_u32_to_u64(d_n_cnt, d_n_off, n_q, d_n_off + n_q, B.a + L.scan, s))) return rc;
-    if ((rc = scan_u32_to_u64(d_a_cnt, d_a_off, n_q, d_a_off + n_q, B.a + L.scan, s))) return rc;
-    PAG_HIP_TRY(hipEventRecord(B.ev[1], s));
+    if ((rc = scan_u32_to_u64(d_n_cnt, d_n_off, n_q, d_n_off + n_q, B.at<char>(L.scan), s))) return rc;
+    if ((rc = scan_u32_to_u64(d_a_cnt, d_a_off, n_q, d_a_off + n_q, B.at<char>(L.scan), s)) || (rc = B.end(QueryCall::COUNT))) return rc;
     PAG_HIP_TRY(hipMemcpyAsync(node_off, d_n_off, (n_q + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     PAG_HIP_TRY(hipMemcpyAsync(alt_off, d_a_off, (n_q + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     if (status) PAG_HIP_TRY(hipMemcpyAsync(status, d_status, n_q * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    PAG_HIP_TRY(hipStreamSynchronize(s));
-    const uint64_t total_n = node_off[n_q], total_a = alt_off[n_q];
-    *n_nodes = total_n;
-    *n_alts = total_a;
-    float ms = 0, ms2 = 0;
-    PAG_HIP_TRY(hipEventElapsedTime(&ms, B.ev[0], B.ev[1]));
-    if (ms_kernels) *ms_kernels = ms;
+    if ((rc = B.done(QueryCall::COUNT, ms_kernels))) return rc;
+    const uint64_t total_n = *n_nodes = node_off[n_q], total_a = *n_alts = alt_off[n_q];
     if (total_n > node_cap || total_a > alt_cap) {
         set_error("pag_walk_straight_batch: %llu path entries and %llu alternatives, room for %llu and %llu", (unsigned long long)total_n,
                   (unsigned long long)total_a, (unsigned long long)node_cap, (unsigned long long)alt_cap);
         return PAG_ERANGE;
     }
     if (total_n == 0) return PAG_OK;
-    if ((rc = B.alloc(&B.nodes, total_n)) || (rc = B.alloc(&B.alts, total_a))) return rc;
-    PAG_HIP_TRY(hipEventRecord(B.ev[2], s));
-    k_walk_query<true><<<grid, dim3(256), 0, s>>>(G, W, d_q, n_q, nullptr, nullptr, nullptr, d_n_off, d_a_off, B.nodes, total_n, B.alts, total_a, B.paths,
+    if ((rc = B.alloc(&d_nodes, total_n)) || (rc = B.alloc(&d_alts, total_a)) || (rc = B.begin(QueryCall::FILL))) return rc;
+    k_walk_query<true><<<grid, dim3(256), 0, s>>>(G, W, d_q, n_q, nullptr, nullptr, nullptr, d_n_off, d_a_off, d_nodes, total_n, d_alts, total_a, d_paths,
                                                   stride);
     PAG_HIP_TRY(hipGetLastError());
-    PAG_HIP_TRY(hipEventRecord(B.ev[3], s));
-    PAG_HIP_TRY(hipMemcpyAsync(nodes, B.nodes, total_n * sizeof(pag_walk_node), hipMemcpyDeviceToHost, s));
-    if (total_a) PAG_HIP_TRY(hipMemcpyAsync(alts, B.alts, total_a * sizeof(pag_succ), hipMemcpyDeviceToHost, s));
-    PAG_HIP_TRY(hipStreamSynchronize(s));
-    PAG_HIP_TRY(hipEventElapsedTime(&ms2, B.ev[2], B.ev[3]));
-    if (ms_kernels) *ms_kernels = (double)ms + (double)ms2;
-    return PAG_OK;
+    if ((rc = B.end(QueryCall::FILL))) return rc;
+    PAG_HIP_TRY(hipMemcpyAsync(nodes, d_nodes, total_n * sizeof(pag_walk_node), hipMemcpyDeviceToHost, s));
+    if (total_a) PAG_HIP_TRY(hipMemcpyAsync(alts, d_alts, total_a * sizeof(pag_succ), hipMemcpyDeviceToHost, s));
+    return B.done(QueryCall::FILL, ms_kernels);
 }
 
 }  // extern "C"

@@ -229,6 +229,7 @@ def test_arguments_are_checked_before_a_device_is_touched():
     total = C.c_uint64(5)
     off = np.zeros(2, dtype=np.uint64)
     assert hip.pag_successors_batch(None, None, 0, 0, 0.15, off.ctypes.data, None, None, 0, C.byref(total), None) == -22
+    assert b"null" in hip.pag_last_error()
     assert total.value == 0
     assert hip.pag_successors_batch_bytes(0, 0) == 0
     assert hip.pag_successors_batch_bytes(1000, 10) >= 1000 * (16 + 8 + 4 + 4) + 10 * 24
