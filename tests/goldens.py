@@ -53,6 +53,33 @@ def generate_case(spec, dest):
     return synth.generate(synth.Spec(**spec["spec"]), dest)
 
 
+_AS_STORED = bytearray(b"A" * 256)  # (CompressedSeq: C / c, G / g, T / t keep their letter, every other byte is stored as A)
+for _c in b"CGTcgt":
+    _AS_STORED[_c] = _c & 0xDF
+_AS_STORED = bytes(_AS_STORED)
+
+
+def reference_fasta(path):
+    """[(name, sequence)] of a FASTA file as the reference's reader takes it (SeqHelper::loadFromFasta + AutoSeqDatabase +
+    CompressedSeq; pinned by tests/test_loader_pins.py): lines as std::getline cuts them, only `>` starts a record, the name is the
+    first token of the header minus its first character, and EVERY byte of the other lines is a base — a CR too — stored as
+    C, G or T (either case) or else as A.  The sequence comes back as the stored letters."""
+    lines = open(path, "rb").read().split(b"\n")
+    if lines and lines[-1] == b"":
+        lines.pop()
+    out, glued = [], []
+    for ln in lines:
+        if ln.startswith(b">"):
+            tok = ln.split()
+            out.append([tok[0][1:].decode() if tok else "", glued])
+            glued = []
+        elif out:
+            out[-1][1].append(ln)
+        else:
+            glued.append(ln)  # (text before the first header is glued to the front of the first record)
+    return [(n, b"".join(parts).translate(_AS_STORED).decode()) for n, parts in out]
+
+
 def golden_graph(name):
     return gzip.open(os.path.join(GOLDEN, name, "graph.txt.gz"), "rb").read()
 

@@ -1,6 +1,7 @@
 // tests/harness/pagh_test.cpp — TEST SUPPORT (never part of the product).
 // Thin C wrapper over the product's host input pipeline so that Python tests (ctypes) can load a
 // pagraph input directory and hand the SAME flat pag_build_input to both the HIP library and the oracle.
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <exception>
@@ -174,5 +175,77 @@ extern "C" int pagt_aln_filter_check(const char *path, uint64_t mod, uint64_t re
     } catch (const std::exception &e) {
         std::fprintf(stderr, "pagt_aln_filter_check: %s\n", e.what());
         return 1;
+    }
+}
+
+// test hooks for the loader pins (tests/test_loader_pins.py): the product's SeqDb / AlnDb of one file written as text, line for
+// line in the format oracle/ref_harness/loader_dump.cpp prints the reference's databases in (modes seq, mecat, mummer), so
+// that a failing test can name its first differing line.
+namespace {
+std::string hexOf(const std::string &s) {
+    if (s.empty()) return "-";
+    static const char *digits = "0123456789abcdef";
+    std::string out;
+    for (unsigned char c : s) {
+        out.push_back(digits[c >> 4]);
+        out.push_back(digits[c & 15]);
+    }
+    return out;
+}
+}  // namespace
+
+extern "C" int pagt_seqdb_dump(const char *path, const char *outPath) {
+    try {
+        pagh::SeqDb db(path);
+        std::FILE *f = std::fopen(outPath, "wb");
+        if (!f) return 1;
+        std::vector<std::string> names;
+        for (std::size_t i = 0; i < db.size(); ++i) {
+            const std::string s = db.toString(i, true);
+            std::fprintf(f, "R %zu %s %u %s\n", i, hexOf(db.name(i)).c_str(), db.length(i), s.empty() ? "-" : s.c_str());
+            names.push_back(db.name(i));
+        }
+        std::sort(names.begin(), names.end());
+        names.erase(std::unique(names.begin(), names.end()), names.end());
+        for (const std::string &n : names) std::fprintf(f, "M %s %zu\n", hexOf(n).c_str(), db.id(n));
+        return std::fclose(f) == 0 ? 0 : 1;
+    } catch (const std::exception &e) {
+        std::fprintf(stderr, "pagt_seqdb_dump: %s\n", e.what());
+        return 1;
+    }
+}
+
+// flavor: 0 = Mecat, 1 = MummerV2.  filter: 0 = none, 1 = an AlnRecordFilter that keeps the records whose query name ends in a
+// byte of odd value (no name: not kept).  Returns 0 = parsed from the text, 1 = loaded from the packed sidecar, -1 = failed.
+extern "C" int pagt_alndb_dump(const char *path, int flavor, int filter, const char *outPath) {
+    try {
+        pagh::AlnRecordFilter keepOdd = [](const char *name, std::size_t len) { return len > 0 && (static_cast<unsigned char>(name[len - 1]) & 1u) != 0; };
+        pagh::AlnDb db(path, flavor == 0 ? pagh::AlnDb::Flavor::Mecat : pagh::AlnDb::Flavor::MummerV2, filter ? keepOdd : pagh::AlnRecordFilter());
+        std::FILE *f = std::fopen(outPath, "wb");
+        if (!f) return -1;
+        for (std::size_t i = 0; i < db.size(); ++i) {
+            const pagh::AlnRecord &r = db[i];
+            std::string q(r.nCols, '0'), t(r.nCols, '0');
+            std::uint32_t nEmit = 0, nRadv = 0;
+            for (std::size_t c = 0; c < r.nCols; ++c) {
+                const unsigned cls = db.colClass(r, c);
+                if (cls & 1u) q[c] = '1';
+                if (cls & 2u) t[c] = '1';
+                nEmit += cls != 1u;
+                nRadv += cls != 2u;
+            }
+            if (nEmit != r.nEmit || nRadv != r.nRadv) {  // (the two per-record counts are functions of the classes)
+                std::fprintf(stderr, "pagt_alndb_dump: record %zu: nEmit %u nRadv %u, its classes give %u %u\n", i, r.nEmit, r.nRadv, nEmit, nRadv);
+                std::fclose(f);
+                return -1;
+            }
+            std::fprintf(f, "A %zu %s %s %s %zu %zu %zu %zu %zu %s %s\n", i, hexOf(r.queryName).c_str(), hexOf(r.refName).c_str(), r.forward ? "F" : "R",
+                         r.score, r.queryBegin, r.queryEnd, r.refBegin, r.refEnd, q.empty() ? "-" : q.c_str(), t.empty() ? "-" : t.c_str());
+        }
+        if (std::fclose(f) != 0) return -1;
+        return db.fromSidecar() ? 1 : 0;
+    } catch (const std::exception &e) {
+        std::fprintf(stderr, "pagt_alndb_dump: %s\n", e.what());
+        return -1;
     }
 }

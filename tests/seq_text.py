@@ -116,17 +116,8 @@ def expected_bytes(records, k):
 
 
 def read_fasta(path):
-    seqs, cur = [], None
-    for ln in open(path):
-        if ln.startswith(">"):
-            if cur is not None:
-                seqs.append("".join(cur))
-            cur = []
-        elif cur is not None:
-            cur.append(ln.strip().upper())
-    if cur is not None:
-        seqs.append("".join(cur))
-    return seqs
+    """the sequences of a FASTA file as the reference stores them (goldens.reference_fasta)"""
+    return [seq for _, seq in goldens.reference_fasta(path)]
 
 
 def case_sequences(name, work):

@@ -18,7 +18,7 @@ def test_restatement_reproduces_every_line_of_every_golden_dump(workdir):
     as the oracle for records no golden has (no golden has a step <= 0, a count above a few hundred, a coordinate of ten
     digits ...)."""
     cases = dump_text.dump_cases()
-    assert len(cases) == 9
+    assert len(cases) == 10
     n_lines = n_rev = n_noctg = longest = 0
     min_step = None
     for name in cases:
@@ -36,9 +36,9 @@ def test_restatement_reproduces_every_line_of_every_golden_dump(workdir):
                 n_noctg += rec[1] == 0
                 longest = max(longest, len(ln))
                 min_step = rec[4] if min_step is None else min(min_step, rec[4])
-    assert n_lines == 26531
-    assert n_rev == 6674
-    assert n_noctg == 1294
+    assert n_lines == 29473
+    assert n_rev == 8162
+    assert n_noctg == 1392
     assert longest == 46
     assert min_step > 0
 

@@ -1,7 +1,10 @@
-"""CPU: the thread-pool sequence loaders (mapped file, parallel line index, FASTA records packed by base ranges, FASTQ records
-packed per read) against the sequential getline loops they replace (PAGH_SEQUENTIAL_LOADERS=1), on inputs with the
-corner cases the reference's reader has: text before the first header, empty lines, CRLF, no final newline, lower case,
-other letters, duplicate names, a lone header, an empty file."""
+"""CPU: OUR two sequence loaders against each other — the thread-pool loaders (mapped file, parallel line index, FASTA records
+packed by base ranges, FASTQ records packed per read) and the sequential getline loops they replace
+(PAGH_SEQUENTIAL_LOADERS=1) — on inputs with the corner cases the reference's reader has: text before the first header,
+empty lines, CRLF, no final newline, lower case, other letters, duplicate names, a lone header, an empty file.  Both sides are
+the product's, so this says that they agree, not what the files mean: that is pinned to the reference's own readers in
+tests/test_loader_pins.py (the same nine files among others).  The record filter and the pack window of a sharded build are
+checked here against the unfiltered parse."""
 import ctypes as C
 import os
 import subprocess

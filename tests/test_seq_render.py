@@ -18,7 +18,7 @@ def test_restatement_reproduces_every_golden_fasta_from_the_golden_dumps(workdir
     the oracle for records no golden has.  The counts say what the goldens reach: steps read through the contig space, through
     the reference space, on a reverse strand, and positions rounded exactly at .5."""
     cases = seq_text.fasta_cases()
-    assert len(cases) == 7
+    assert len(cases) == 8
     counts = seq_text.Counts()
     n_files = n_pieces = n_bases = 0
     for name in cases:
@@ -35,10 +35,10 @@ def test_restatement_reproduces_every_golden_fasta_from_the_golden_dumps(workdir
             assert b"".join(got).decode() == body, f"{name}/{f}"
             n_files += 1
             n_bases += len(body)
-    assert n_files == 8
-    assert n_pieces == 18
-    assert n_bases == 81329
-    assert (counts.short, counts.long, counts.long_bases) == (22431, 496, 6575)
+    assert n_files == 9
+    assert n_pieces == 20
+    assert n_bases == 90258
+    assert (counts.short, counts.long, counts.long_bases) == (25371, 496, 6575)
     assert (counts.ctg, counts.ref, counts.reverse, counts.half) == (472, 24, 2, 14)
     assert counts.pos_similar == 0  # (no golden decides by isPosSimilar: the constructed records of the GPU tests do)
 

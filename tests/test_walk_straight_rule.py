@@ -96,6 +96,7 @@ COMMON = {
     ("ignore_output_t1", "0_0_0"): None, ("ignore_output_t1", "0_1_0"): None,
     ("join_fwd_t1", "0_0_0"): None, ("join_fwd_t1", "0_1_0"): None,
     ("join_rev_t16", "0_0_0"): None, ("join_rev_t16", "0_1_1"): 1437,
+    ("messy_inputs_t1", "0_0_0"): None, ("messy_inputs_t1", "0_1_1"): 1479,
     ("succ_corners_t8", "0_0_0"): None, ("succ_corners_t8", "0_1_0"): None,
     ("three_ctg_multi_t4", "0_0_0"): 1088, ("three_ctg_multi_t4", "0_1_1"): None, ("three_ctg_multi_t4", "0_2_0"): None,
     ("two_blocks_both_orient_t16", "0_0_0"): None, ("two_blocks_both_orient_t16", "0_1_1"): 1460,
