@@ -803,17 +803,7 @@ int pag_shard_extract_for(pag_graph *g, const pag_build_input *in, uint64_t lo, 
 }
 
 int pag_shard_take(pag_graph *g, uint32_t *tkey, uint64_t *tval, uint32_t *ekey, uint64_t *eval) {
-    if (!g) return PAG_EINVAL;
-    PAG_HIP_TRY(hipSetDevice(g->device));
-    hipStream_t s = g->stream;
-    const uint64_t T = g->shard_x[0], E = g->shard_x[1];
-    const StreamPtrs x = streams_at(g, g->shard_in0[0], g->shard_in0[1]);
-    if (T) PAG_HIP_TRY(hipMemcpyAsync(tkey, x.tkey, T * 4, hipMemcpyDeviceToDevice, s));
-    if (T) PAG_HIP_TRY(hipMemcpyAsync(tval, x.tval, T * 8, hipMemcpyDeviceToDevice, s));
-    if (E) PAG_HIP_TRY(hipMemcpyAsync(ekey, x.ekey, E * 4, hipMemcpyDeviceToDevice, s));
-    if (E) PAG_HIP_TRY(hipMemcpyAsync(eval, x.eval, E * 8, hipMemcpyDeviceToDevice, s));
-    PAG_HIP_TRY(hipStreamSynchronize(s));
-    return PAG_OK;
+    return g ? pag_shard_take_part(g, 0, g->shard_x[0], tkey, tval, 0, g->shard_x[1], ekey, eval) : PAG_EINVAL;
 }
 
 int pag_shard_take_part(pag_graph *g, uint64_t t_off, uint64_t t_n, uint32_t *tkey, uint64_t *tval, uint64_t e_off, uint64_t e_n, uint32_t *ekey,
@@ -826,13 +816,8 @@ int pag_shard_take_part(pag_graph *g, uint64_t t_off, uint64_t t_n, uint32_t *tk
         return PAG_EINVAL;
     }
     PAG_HIP_TRY(hipSetDevice(g->device));
-    hipStream_t s = g->stream;
-    const StreamPtrs x = streams_at(g, g->shard_in0[0], g->shard_in0[1]);
-    if (t_n) PAG_HIP_TRY(hipMemcpyAsync(tkey, x.tkey + t_off, t_n * 4, hipMemcpyDeviceToDevice, s));
-    if (t_n) PAG_HIP_TRY(hipMemcpyAsync(tval, x.tval + t_off, t_n * 8, hipMemcpyDeviceToDevice, s));
-    if (e_n) PAG_HIP_TRY(hipMemcpyAsync(ekey, x.ekey + e_off, e_n * 4, hipMemcpyDeviceToDevice, s));
-    if (e_n) PAG_HIP_TRY(hipMemcpyAsync(eval, x.eval + e_off, e_n * 8, hipMemcpyDeviceToDevice, s));
-    PAG_HIP_TRY(hipStreamSynchronize(s));
+    if (int rc = copy_streams(streams_at(g, g->shard_in0[0], g->shard_in0[1]), t_off, t_n, e_off, e_n, tkey, tval, ekey, eval, g->stream)) return rc;
+    PAG_HIP_TRY(hipStreamSynchronize(g->stream));
     return PAG_OK;
 }
 
@@ -841,14 +826,10 @@ int pag_shard_build(pag_graph *g, const uint32_t *tkey, const uint64_t *tval, ui
     if (!g || t1 > n_t || e1 > n_e || (n_t && (!tkey || !tval)) || (n_e && (!ekey || !eval))) return PAG_EINVAL;
     PAG_HIP_TRY(hipSetDevice(g->device));
     free_graph_results(g);
-    hipStream_t s = g->stream;
     int rc;
     DevBuf b_tk0(g, ps::TK0), b_tv0(g, ps::TV0), b_ek0(g, ps::EK0), b_ev0(g, ps::EV0);
     if ((rc = b_tk0.alloc((n_t + 1) * 4)) || (rc = b_tv0.alloc((n_t + 1) * 8)) || (rc = b_ek0.alloc((n_e + 1) * 4)) || (rc = b_ev0.alloc((n_e + 1) * 8))) return rc;
-    if (n_t) PAG_HIP_TRY(hipMemcpyAsync(b_tk0.p, tkey, n_t * 4, hipMemcpyDeviceToDevice, s));
-    if (n_t) PAG_HIP_TRY(hipMemcpyAsync(b_tv0.p, tval, n_t * 8, hipMemcpyDeviceToDevice, s));
-    if (n_e) PAG_HIP_TRY(hipMemcpyAsync(b_ek0.p, ekey, n_e * 4, hipMemcpyDeviceToDevice, s));
-    if (n_e) PAG_HIP_TRY(hipMemcpyAsync(b_ev0.p, eval, n_e * 8, hipMemcpyDeviceToDevice, s));
+    if ((rc = copy_streams(StreamPtrs{tkey, tval, ekey, eval}, 0, n_t, 0, n_e, b_tk0.p, b_tv0.p, b_ek0.p, b_ev0.p, g->stream))) return rc;
     EventSet ev;
     if ((rc = ev.create())) return rc;
     Extracted x;
@@ -918,16 +899,7 @@ int pag_shard_import(pag_graph *g, const pag_shard_slice *parts, uint32_t n_part
         }
         at += P.n_t;
         ae += P.n_e;
-        for (int q = 0; q < 2; ++q) {
-            st.merge_edge[q] += P.stats.merge_edge[q];
-            st.total_pos[q] += P.stats.total_pos[q];
-            st.merge_pos[q] += P.stats.merge_pos[q];
-            st.n_tuples[q] += P.stats.n_tuples[q];
-            st.n_edges[q] += P.stats.n_edges[q];
-        }
-        st.n_nodes += P.stats.n_nodes;
-        st.n_pos += P.stats.n_pos;
-        st.n_uniq_edges += P.stats.n_uniq_edges;
+        add_stats(st, P.stats);
     }
     PAG_HIP_TRY(hipStreamSynchronize(s));
     free_graph_results(g);

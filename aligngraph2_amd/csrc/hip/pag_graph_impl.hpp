@@ -251,6 +251,30 @@ inline StreamPtrs streams_at(const pag_graph *g, int t_in0, int e_in0) {
     return StreamPtrs{(const uint32_t *)g->pool[t_in0 ? ps::TK0 : ps::TK1].p, (const uint64_t *)g->pool[t_in0 ? ps::TV0 : ps::TV1].p,
                       (const uint32_t *)g->pool[e_in0 ? ps::EK0 : ps::EK1].p, (const uint64_t *)g->pool[e_in0 ? ps::EV0 : ps::EV1].p};
 }
+// the tuples [t_off, +t_n) and the edges [e_off, +e_n) of the streams `x` to the starts of the four arrays, queued on s
+inline int copy_streams(const StreamPtrs &x, uint64_t t_off, uint64_t t_n, uint64_t e_off, uint64_t e_n, void *tkey, void *tval, void *ekey, void *eval,
+                        hipStream_t s) {
+    if (t_n) PAG_HIP_TRY(hipMemcpyAsync(tkey, x.tkey + t_off, t_n * 4, hipMemcpyDeviceToDevice, s));
+    if (t_n) PAG_HIP_TRY(hipMemcpyAsync(tval, x.tval + t_off, t_n * 8, hipMemcpyDeviceToDevice, s));
+    if (e_n) PAG_HIP_TRY(hipMemcpyAsync(ekey, x.ekey + e_off, e_n * 4, hipMemcpyDeviceToDevice, s));
+    if (e_n) PAG_HIP_TRY(hipMemcpyAsync(eval, x.eval + e_off, e_n * 8, hipMemcpyDeviceToDevice, s));
+    return PAG_OK;
+}
+
+// the count lines and sizes of a graph made of parts (slices of owners, selections for a region) are the sums over the parts
+inline void add_stats(pag_build_stats &st, const pag_build_stats &p) {
+    for (int q = 0; q < 2; ++q) {
+        st.merge_edge[q] += p.merge_edge[q];
+        st.total_pos[q] += p.total_pos[q];
+        st.merge_pos[q] += p.merge_pos[q];
+        st.n_tuples[q] += p.n_tuples[q];
+        st.n_edges[q] += p.n_edges[q];
+    }
+    st.n_nodes += p.n_nodes;
+    st.n_pos += p.n_pos;
+    st.n_uniq_edges += p.n_uniq_edges;
+}
+inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // Both extraction passes for the reads [lo, hi) of the emission order and the records per (owner, pass) of the two streams
 // (pag_api.hip): pag_shard_extract_range without its partition — the streams stay as extract_stage left them, no ping-pong

@@ -10,7 +10,7 @@
 //
 // Order argument for bit-identity with one GPU: see include/pagraph_hip.h (pag_shard_*) — rank r extracts the r-th contiguous
 // range of the emission order, owners lay the received records out as [pass 1 from rank 0] .. [pass 1 from rank N-1]
-// [pass 2 from rank 0] .. and sort stably by k-mer.
+// [pass 2 from rank 0] .. and sort stably by k-mer.  Where a record lies in that order is serial_layout.hpp's to say, not this file's.
 #include <dirent.h>
 #include <dlfcn.h>
 #include <fcntl.h>
@@ -31,6 +31,7 @@
 
 #include "dev_call.hpp"
 #include "pag_graph_impl.hpp"
+#include "serial_layout.hpp"
 
 namespace {
 
@@ -67,7 +68,7 @@ struct Rccl {
     }
 };
 
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+using pagdev::now_s;
 
 // start time of a process in clock ticks since boot (field 22 of /proc/<pid>/stat), 0 if it does not exist: (pid, start
 // time) names ONE process for as long as the machine is up
@@ -427,70 +428,16 @@ int pag_comm_gather_v(pag_comm *c, const void *mine, uint64_t bytes, int root, v
     return at <= out_cap ? PAG_OK : PAG_ERANGE;
 }
 
-// all-to-all(v) of DEVICE memory: send_bytes[d] consecutive bytes of `send` go to rank d, recv_bytes[s] bytes arrive from
-// rank s, in rank order on both sides
-int pag_comm_all_to_all_v(pag_comm *c, const void *send, const uint64_t *send_bytes, void *recv, const uint64_t *recv_bytes) {
-    if (!c || !send_bytes || !recv_bytes) return PAG_EINVAL;
-    const uint64_t n = c->seq++;
-    PAG_HIP_TRY(hipSetDevice(c->device));
-    std::vector<uint64_t> so(c->world + 1, 0), ro(c->world + 1, 0);
-    for (int r = 0; r < c->world; ++r) {
-        so[r + 1] = so[r] + send_bytes[r];
-        ro[r + 1] = ro[r] + recv_bytes[r];
-        if (r != c->rank) c->bytes_sent += send_bytes[r];
-    }
-    if (send_bytes[c->rank] != recv_bytes[c->rank]) return PAG_EINVAL;
-    if (c->use_rccl) {
-        // a grouped Send / Recv whose peer never arrives waits for ever: the ranks first meet through the rendezvous directory
-        // (where a failed peer's abort marker is seen), and only a complete set of ranks enters RCCL
-        if (c->world > 1) {
-            const int brc = pag_comm_barrier(c);
-            if (brc) return brc;
-        }
-        ncclResult_t rc = c->rccl.GroupStart();
-        for (int r = 0; r < c->world && rc == ncclSuccess; ++r) {
-            if (send_bytes[r]) rc = c->rccl.Send((const char *)send + so[r], send_bytes[r], ncclUint8, r, c->comm, c->stream);
-            if (rc == ncclSuccess && recv_bytes[r]) rc = c->rccl.Recv((char *)recv + ro[r], recv_bytes[r], ncclUint8, r, c->comm, c->stream);
-        }
-        const ncclResult_t rc2 = c->rccl.GroupEnd();
-        if (rc != ncclSuccess || rc2 != ncclSuccess) {
-            pagdev::set_error("pag_comm_all_to_all_v: RCCL error %s", c->rccl.GetErrorString ? c->rccl.GetErrorString(rc != ncclSuccess ? rc : rc2) : "?");
-            return PAG_EFAULT;
-        }
-        PAG_HIP_TRY(hipStreamSynchronize(c->stream));
-        return PAG_OK;
-    }
-    // through the rendezvous directory (single-device test boxes)
-    std::vector<char> host;
-    int rc;
-    for (int d = 0; d < c->world; ++d) {
-        if (d == c->rank) continue;
-        host.resize(send_bytes[d]);
-        if (send_bytes[d]) PAG_HIP_TRY(hipMemcpy(host.data(), (const char *)send + so[d], send_bytes[d], hipMemcpyDeviceToHost));
-        if ((rc = c->put_file(c->path("a", n, c->rank, d), host.data(), send_bytes[d]))) return rc;
-    }
-    if (send_bytes[c->rank]) PAG_HIP_TRY(hipMemcpy((char *)recv + ro[c->rank], (const char *)send + so[c->rank], send_bytes[c->rank], hipMemcpyDeviceToDevice));
-    for (int s = 0; s < c->world; ++s) {
-        if (s == c->rank) continue;
-        if ((rc = c->get_file(c->path("a", n, s, c->rank), host, true))) return rc;
-        if (host.size() != recv_bytes[s]) {
-            pagdev::set_error("pag_comm_all_to_all_v: %zu bytes from rank %d, %llu expected", host.size(), s, (unsigned long long)recv_bytes[s]);
-            return PAG_EFAULT;
-        }
-        if (recv_bytes[s]) PAG_HIP_TRY(hipMemcpy((char *)recv + ro[s], host.data(), recv_bytes[s], hipMemcpyHostToDevice));
-    }
-    return PAG_OK;
-}
-
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------------------------------
-// A bulk exchange that runs IN THE BACKGROUND (round 5): several device arrays, each an all-to-all(v) as above, begun by
-// xchg_begin and waited for by xchg_end, so that the next piece of work of the call's own stream — the next chunk's
-// extraction, the next destination's selection — runs beside it.  RCCL: the grouped sends / receives of all arrays are
-// enqueued on the communicator's stream (a stream of its own, non-blocking) and xchg_end waits for that stream.  Files of the
-// rendezvous directory (ranks that share a device): a helper thread does what pag_comm_all_to_all_v does, with copies on the
-// communicator's stream.  One exchange at a time per communicator.
+// The bulk exchange: several device arrays, each an all-to-all(v) — sb[d] consecutive bytes of `send` go to rank d, rb[s] bytes
+// arrive from rank s, in rank order on both sides.  It runs IN THE BACKGROUND (round 5), begun by xchg_begin and waited for by
+// xchg_end, so that the next piece of work of the call's own stream — the next chunk's extraction, the next destination's
+// selection — runs beside it.  RCCL: the grouped sends / receives of all arrays are enqueued on the communicator's stream (a
+// stream of its own, non-blocking) and xchg_end waits for that stream.  Files of the rendezvous directory (ranks that share a
+// device: the single-GPU test boxes): a helper thread passes them, with copies on the communicator's stream.  One exchange at a
+// time per communicator.
 // ---------------------------------------------------------------------------------------------------------------------
 namespace {
 struct Xchg {
@@ -567,7 +514,9 @@ int xchg_begin(pag_comm *c, Xchg &X, std::vector<XchgArr> arrs) {
     }
     X.t_begin = now_s();
     if (c->use_rccl) {
-        if (c->world > 1) {  // (only a complete set of ranks enters RCCL: see pag_comm_all_to_all_v)
+        // a grouped Send / Recv whose peer never arrives waits for ever: the ranks first meet through the rendezvous directory
+        // (where a failed peer's abort marker is seen), and only a complete set of ranks enters RCCL
+        if (c->world > 1) {
             const int brc = pag_comm_barrier(c);
             if (brc) return brc;
         }
@@ -640,337 +589,362 @@ struct XchgGuard {  // (an error return between begin and end must not leave a j
 };
 }  // namespace
 
-extern "C" {
+// all-to-all(v) of DEVICE memory, one array, waited for: the exchange above, begun and ended
+extern "C" int pag_comm_all_to_all_v(pag_comm *c, const void *send, const uint64_t *send_bytes, void *recv, const uint64_t *recv_bytes) {
+    if (!c || !send_bytes || !recv_bytes) return PAG_EINVAL;
+    PAG_HIP_TRY(hipSetDevice(c->device));
+    // The exchange works on the communicator's own stream, which is ordered behind no other: what the caller queued on the device
+    // before this call — the null stream's work included — is waited for here, so that `send` holds what the caller put there.
+    PAG_HIP_TRY(hipDeviceSynchronize());
+    Xchg X;
+    XchgGuard guard{X};
+    const int rc = xchg_begin(c, X, {XchgArr{send, recv, {send_bytes, send_bytes + c->world}, {recv_bytes, recv_bytes + c->world}}});
+    return rc ? rc : xchg_end(X);
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
-// pag_shard_run: the sharded build of one block behind one call (every rank calls it with the same prepared input).
-//   extract own read range -> all-to-all(v) of the tuple / edge streams -> K2-K4 on the owned k-mer range -> every rank's
-//   region selected from the slice -> all-to-all(v) of the selections, received straight into the handle's graph buffers ->
-//   region set, the build's memory released.
+// pag_shard_run: the sharded build of one block behind one call (every rank calls it with the same prepared input).  Its stages:
+//   1. exchange_streams        own read range extracted in chunks, every chunk's tuple / edge streams to their owners
+//   2. lay_out_owned           what arrived, in the owner's canonical order (the plan of serial_layout.hpp)
+//   3. build_owned             K2-K4 on the owned k-mer range
+//   4. exchange_regions_ring   every rank's region selected from the slice and sent to it, a selection beside the next one
+//      / exchange_regions_whole  (PAG_SHARD_PIPELINE=0) all selections first, then seven whole all-to-all(v)s
+//   5. adopt_region            what arrived becomes the handle's graph, region set, the build's memory released
 // regions[world]: what every rank traverses (the same on all ranks); total: the block's count lines.
 // ---------------------------------------------------------------------------------------------------------------------
-static int shard_run(pag_graph *g, pag_comm *c, const pag_build_input *in, const pag_region *regions, pag_build_stats *total);
-int pag_shard_run(pag_graph *g, pag_comm *c, const pag_build_input *in, const pag_region *regions, pag_build_stats *total) {
+namespace {
+using namespace pagdev;
+
+// PAGRAPH_TIMING=1: one line per rank and block on stderr — seconds per stage of this call (the device idle at every boundary)
+// and the payload that left the rank in each of the two bulk exchanges.  Without it the clock neither synchronises nor counts.
+struct StageClock {
+    const bool on = env_timing();
+    double t_prev = now();
+    double now() const {
+        if (on) hipDeviceSynchronize();
+        return now_s();
+    }
+    double lap() {  // seconds since the lap before
+        if (!on) return 0;
+        const double t = now(), d = t - t_prev;
+        t_prev = t;
+        return d;
+    }
+};
+
+// The books of a loop whose step i runs beside the exchange begun after step i - 1 (host clock): seconds of the steps, of the
+// exchanges, of the exchanges that passed beside a step, and of the whole loop; [step0, step1]: the step that ended last.
+struct OverlapBooks {
+    double step = 0, xfer = 0, hidden = 0, loop = 0;
+    double t_loop = 0, step0 = 0, step1 = 0;
+};
+// the exchange under way, if there is one, is waited for and booked; beside_step: it travelled beside the step that has just ended
+int xchg_end_booked(Xchg &X, OverlapBooks &B, bool beside_step) {
+    const bool was_active = X.active;
+    const int rc = xchg_end(X);
+    if (rc || !was_active) return rc;
+    B.xfer += X.t_done - X.t_begin;
+    if (beside_step) B.hidden += std::max(0.0, std::min(X.t_done, B.step1) - std::max(X.t_begin, B.step0));
+    return PAG_OK;
+}
+
+constexpr int NA = ps::GRAPH_ARRS, NT = ps::GRAPH_TUPLE_ARRS;  // the seven arrays of a graph, the first four per tuple
+ps::Id send_slot(int a) { return ps::family(ps::SEND, a); }    // the send buffers of the region exchange
+
+struct ShardRun {
+    pag_graph *g;
+    pag_comm *c;
+    const pag_build_input *in;
+    const pag_region *regions;
+    const int W, me;
+    hipStream_t s;
+    StageClock clock;
+    // 1 -> 2: counts[chunk_range(rank, C, chunk)][owner][4] (serial_layout.hpp), the chunks' arrays (tkey tval ekey eval each)
+    int C = 4;
+    std::vector<uint64_t> counts;
+    struct ChunkBufs {
+        void *send[4] = {}, *recv[4] = {};  // this rank's chunk, partitioned by owner; what the ranks sent of theirs
+    };
+    std::vector<ChunkBufs> cb;
+    DevCall tmp{"pag_shard_run"}, sent{"pag_shard_run"};  // the chunks as received; this rank's copies of them on their way out
+    // 2 -> 3: the owner's streams and the plan they were laid out by, its sizes with it ([0] tuples, [1] edges)
+    DevBuf own[4];
+    ReceivePlan plan[2];
+    // 4 -> 5: the region in the import slots, the statistics of what owner o selected for this rank
+    uint64_t T = 0, E = 0;
+    std::vector<pag_build_stats> from_owner = std::vector<pag_build_stats>((size_t)W);
+    // the [shard timing] line
+    OverlapBooks tuple_books, region_books;
+    double s_layout = 0, s_build = 0, s_owner_order = 0, s_adopt = 0;
+};
+
+// 1. Extraction in CHUNKS, every chunk's partitioned streams on their way to the owners while the next chunk is extracted
+//    (SURVEY.md 8e).  PAG_SHARD_CHUNKS (default 4; 1: the whole range at once).  A chunk's streams are copied out of the
+//    extraction's slots (the next chunk overwrites them) and received into arrays of their own.
+int exchange_streams(ShardRun &R) {
+    pag_graph *g = R.g;
+    const int W = R.W, me = R.me, C = R.C;
+    int rc;
+    const uint64_t n_reads = R.in->reads.n_seqs, r_lo = n_reads * (uint64_t)me / (uint64_t)W, r_hi = n_reads * ((uint64_t)me + 1) / (uint64_t)W;
+    R.counts.assign((size_t)W * C * W * 4, 0);
+    R.cb.resize((size_t)C);
+    std::vector<uint64_t> mine(4 * (size_t)W), all(4 * (size_t)W * W);
+    Xchg X;
+    XchgGuard xguard{X};
+    OverlapBooks &B = R.tuple_books;
+    B.t_loop = now_s();
+    for (int ch = 0; ch < C; ++ch) {
+        const uint64_t lo = r_lo + (r_hi - r_lo) * (uint64_t)ch / (uint64_t)C, hi = r_lo + (r_hi - r_lo) * ((uint64_t)ch + 1) / (uint64_t)C;
+        ShardRun::ChunkBufs &cb = R.cb[(size_t)ch];
+        B.step0 = now_s();
+        if ((rc = pag_shard_extract_range(g, R.in, lo, hi, (uint32_t)W, mine.data()))) return rc;
+        for (int a = 0; a < 4; ++a) {
+            char *q = nullptr;
+            if ((rc = R.sent.alloc(&q, (g->shard_x[a / 2] + 1) * ps::STREAM_ESZ[a]))) return rc;
+            cb.send[a] = q;
+        }
+        const StreamPtrs part = streams_at(g, g->shard_in0[0], g->shard_in0[1]);
+        if ((rc = copy_streams(part, 0, g->shard_x[0], 0, g->shard_x[1], cb.send[0], cb.send[1], cb.send[2], cb.send[3], R.s))) return rc;
+        PAG_HIP_TRY(hipStreamSynchronize(R.s));
+        B.step += (B.step1 = now_s()) - B.step0;
+        if ((rc = pag_comm_all_gather(R.c, mine.data(), mine.size() * 8, all.data()))) return rc;
+        for (int r = 0; r < W; ++r)
+            std::memcpy(&R.counts[(size_t)chunk_range(r, C, ch) * W * 4], &all[(size_t)r * W * 4], (size_t)W * 4 * 8);
+        // the chunk before this one has been travelling beside this extraction
+        if ((rc = xchg_end_booked(X, B, true))) return rc;
+        std::vector<XchgArr> arrs(4);
+        for (int a = 0; a < 4; ++a) {
+            uint64_t tot = 0;
+            arrs[a].sb.resize(W);
+            arrs[a].rb.resize(W);
+            for (int r = 0; r < W; ++r) {
+                arrs[a].sb[r] = range_records(R.counts.data(), W, chunk_range(me, C, ch), r, a / 2) * ps::STREAM_ESZ[a];
+                arrs[a].rb[r] = range_records(R.counts.data(), W, chunk_range(r, C, ch), me, a / 2) * ps::STREAM_ESZ[a];
+                tot += arrs[a].rb[r];
+            }
+            char *q = nullptr;
+            if ((rc = R.tmp.alloc(&q, tot + ps::STREAM_ESZ[a]))) return rc;
+            arrs[a].send = cb.send[a];
+            arrs[a].recv = cb.recv[a] = q;
+        }
+        if ((rc = xchg_begin(R.c, X, std::move(arrs)))) return rc;
+    }
+    if ((rc = xchg_end_booked(X, B, false))) return rc;
+    B.loop = now_s() - B.t_loop;
+    return PAG_OK;
+}
+
+// 2. When the last chunk has arrived the owner lays the pieces out as [pass 1: rank 0 chunk 0, chunk 1 .. rank 1 ..][pass 2: ..] —
+//    the ranks' read ranges and, inside a rank, its chunks are contiguous in emission order, so that is the canonical order
+//    again.  chunked_receive_plan knows where everything lies; here its copies are made.
+int lay_out_owned(ShardRun &R) {
+    int rc;
+    R.sent.release();  // (the chunks' send copies are done with)
+    for (int st = 0; st < 2; ++st) R.plan[st] = chunked_receive_plan(R.counts.data(), R.W, R.C, R.me, st);
+    const ps::Id slot[4] = {ps::OWN_TK, ps::OWN_TV, ps::OWN_EK, ps::OWN_EV};
+    for (int a = 0; a < 4; ++a) {
+        R.own[a] = DevBuf(R.g, slot[a]);
+        if ((rc = R.own[a].alloc((R.plan[a / 2].n + 1) * ps::STREAM_ESZ[a]))) return rc;
+    }
+    for (int a = 0; a < 4; ++a) {
+        const uint64_t esz = ps::STREAM_ESZ[a];
+        for (const ReceivePlan::Copy &cp : R.plan[a / 2].copies)
+            PAG_HIP_TRY(hipMemcpyAsync((char *)R.own[a].p + cp.dst * esz, (const char *)R.cb[cp.chunk].recv[a] + cp.src * esz, cp.n * esz, hipMemcpyDeviceToDevice, R.s));
+    }
+    PAG_HIP_TRY(hipStreamSynchronize(R.s));
+    R.tmp.release();
+    return PAG_OK;
+}
+
+// 3. K2-K4 on what this owner holds
+int build_owned(ShardRun &R) {
+    pag_build_stats mine{};
+    return pag_shard_build(R.g, R.own[0].as<uint32_t>(), R.own[1].as<uint64_t>(), R.plan[0].n, R.plan[0].n1, R.own[2].as<uint32_t>(), R.own[3].as<uint64_t>(),
+                           R.plan[1].n, R.plan[1].n1, R.in->eps, &mine);
+}
+
+// 4. Every rank's region of this owner's slice.  A selection lives in the handle until the next one: it is copied behind the
+//    previous ones into the send buffers, which are sized once for what the selections of all destinations usually add up to — the
+//    slice itself plus the landing zones and halos that several ranks take (1.2x at N = 4, measured) — so that the loops below
+//    neither allocate nor copy what they have already gathered; a block that needs more grows them.
+int reserve_send_buffers(ShardRun &R) {
+    int rc;
+    for (int a = 0; a < NA; ++a) {
+        const uint64_t n_slice = a < NT ? R.g->n_t : R.g->n_e;
+        if ((rc = DevBuf(R.g, send_slot(a)).alloc((n_slice + n_slice / 2 + 1024) * ps::GRAPH_ESZ[a]))) return rc;
+    }
+    return PAG_OK;
+}
+// the selection `sel` behind the at[a] elements array a of the send buffers holds (at: advanced).  A buffer that is too small is
+// grown with its contents kept; X: an exchange that may still read the old array and is waited for first (null: there is none)
+int append_selection(ShardRun &R, const pag_shard_slice &sel, std::vector<uint64_t> &at, Xchg *X) {
+    int rc;
+    const GraphArrays from = arrays_of(sel);
+    for (int a = 0; a < NA; ++a) {
+        const uint64_t n = a < NT ? sel.n_t : sel.n_e, esz = ps::GRAPH_ESZ[a], need = (at[a] + n + 1) * esz;
+        DevBuf b(R.g, send_slot(a));
+        if (b.sl->cap < need && ((X && (rc = xchg_end(*X))) || (rc = b.alloc_keeping(need, at[a] * esz, need + need / 2 + 256)))) return rc;
+        if (n) PAG_HIP_TRY(hipMemcpyAsync((char *)b.sl->p + at[a] * esz, from.p[a], n * esz, hipMemcpyDeviceToDevice, R.s));
+        at[a] += n;
+    }
+    PAG_HIP_TRY(hipStreamSynchronize(R.s));
+    return PAG_OK;
+}
+
+// Ring schedule.  Step i: this owner selects the region of rank (me + i) mod W and receives, from rank (me - i) mod W, that
+// owner's selection for this rank; the selection of step i travels while the one of step i + 1 is made.  What arrives is kept
+// per owner and put in owner order (ascending k-mer ranges) when the last piece is there.
+int exchange_regions_ring(ShardRun &R) {
+    pag_graph *g = R.g;
+    const int W = R.W, me = R.me;
+    int rc;
+    struct StepMsg {  // what an owner selected in this step: its size and count lines
+        uint64_t n_t, n_e;
+        pag_build_stats st;
+    };
+    std::vector<std::vector<void *>> piece((size_t)W, std::vector<void *>(NA, nullptr));  // [owner][array]
+    std::vector<uint64_t> piece_t(W, 0), piece_e(W, 0), at(NA, 0);
+    DevCall rtmp("pag_shard_run");
+    Xchg X;
+    XchgGuard xguard{X};
+    OverlapBooks &B = R.region_books;
+    B.t_loop = now_s();
+    for (int i = 0; i < W; ++i) {
+        const int dst = (me + i) % W, src = (me - i + W) % W;
+        B.step0 = now_s();
+        pag_shard_slice sel{};
+        if ((rc = pag_shard_select(g, &R.regions[dst], &sel))) return rc;
+        const std::vector<uint64_t> at0 = at;
+        if ((rc = append_selection(R, sel, at, &X))) return rc;
+        B.step += (B.step1 = now_s()) - B.step0;
+        std::vector<StepMsg> msg(W);
+        StepMsg mine_msg{sel.n_t, sel.n_e, sel.stats};
+        if ((rc = pag_comm_all_gather(R.c, &mine_msg, sizeof mine_msg, msg.data()))) return rc;
+        if ((rc = xchg_end_booked(X, B, true))) return rc;
+        R.T += piece_t[(size_t)src] = msg[(size_t)src].n_t;  // (every owner is `src` in exactly one step)
+        R.E += piece_e[(size_t)src] = msg[(size_t)src].n_e;
+        R.from_owner[(size_t)src] = msg[(size_t)src].st;
+        if (i == 0) continue;  // this rank's own selection stays where it is: at the front of the send buffers
+        std::vector<XchgArr> xa(NA);
+        for (int a = 0; a < NA; ++a) {
+            const uint64_t n_out = a < NT ? sel.n_t : sel.n_e, n_in = a < NT ? piece_t[(size_t)src] : piece_e[(size_t)src], esz = ps::GRAPH_ESZ[a];
+            char *q = nullptr;
+            if ((rc = rtmp.alloc(&q, (n_in + 1) * esz))) return rc;
+            piece[(size_t)src][a] = q;
+            xa[a].sb.assign(W, 0);
+            xa[a].rb.assign(W, 0);
+            xa[a].sb[(size_t)dst] = n_out * esz;
+            xa[a].rb[(size_t)src] = n_in * esz;
+            xa[a].send = (const char *)g->pool[send_slot(a)].p + at0[a] * esz;
+            xa[a].recv = q;
+        }
+        if ((rc = xchg_begin(R.c, X, std::move(xa)))) return rc;
+    }
+    if ((rc = xchg_end_booked(X, B, false))) return rc;
+    B.loop = now_s() - B.t_loop;
+    R.clock.lap();
+    for (int a = 0; a < NA; ++a) {
+        const uint64_t esz = ps::GRAPH_ESZ[a];
+        DevBuf imp(g, ps::family(ps::IMPORT, a));
+        if ((rc = imp.alloc(((a < NT ? R.T : R.E) + 1) * esz))) return rc;
+        piece[(size_t)me][a] = g->pool[send_slot(a)].p;  // (where the send buffer is NOW: one that grew has moved)
+        uint64_t off = 0;
+        for (int o = 0; o < W; ++o) {  // owner order = ascending k-mer ranges
+            const uint64_t n = a < NT ? piece_t[(size_t)o] : piece_e[(size_t)o];
+            if (n) PAG_HIP_TRY(hipMemcpyAsync((char *)imp.p + off * esz, piece[(size_t)o][a], n * esz, hipMemcpyDeviceToDevice, R.s));
+            off += n;
+        }
+    }
+    PAG_HIP_TRY(hipStreamSynchronize(R.s));
+    rtmp.release();
+    R.s_owner_order = R.clock.lap();
+    return PAG_OK;
+}
+
+// Whole schedule (PAG_SHARD_PIPELINE=0, as until round 5): all selections first, then seven whole all-to-all(v)s, received
+// straight into the import slots — rank order there is owner order, ascending k-mer ranges
+int exchange_regions_whole(ShardRun &R) {
+    pag_graph *g = R.g;
+    const int W = R.W, me = R.me;
+    int rc;
+    std::vector<uint64_t> my_sizes(2 * (size_t)W), all_sizes(2 * (size_t)W * W), at(NA, 0);
+    std::vector<pag_build_stats> stats_to(W), all_stats((size_t)W * W);
+    for (int d = 0; d < W; ++d) {
+        pag_shard_slice sel{};
+        if ((rc = pag_shard_select(g, &R.regions[d], &sel))) return rc;
+        my_sizes[2 * d] = sel.n_t;
+        my_sizes[2 * d + 1] = sel.n_e;
+        stats_to[d] = sel.stats;
+        if ((rc = append_selection(R, sel, at, nullptr))) return rc;
+    }
+    R.region_books.step = R.clock.lap();
+    if ((rc = pag_comm_all_gather(R.c, my_sizes.data(), my_sizes.size() * 8, all_sizes.data()))) return rc;
+    if ((rc = pag_comm_all_gather(R.c, stats_to.data(), stats_to.size() * sizeof(pag_build_stats), all_stats.data()))) return rc;
+    auto size_of = [&](int owner, int dst, int which) { return all_sizes[((size_t)owner * W + dst) * 2 + which]; };
+    for (int o = 0; o < W; ++o) {
+        R.T += size_of(o, me, 0);
+        R.E += size_of(o, me, 1);
+        R.from_owner[(size_t)o] = all_stats[(size_t)o * W + me];
+    }
+    for (int a = 0; a < NA; ++a) {
+        const uint64_t esz = ps::GRAPH_ESZ[a];
+        DevBuf imp(g, ps::family(ps::IMPORT, a));
+        if ((rc = imp.alloc(((a < NT ? R.T : R.E) + 1) * esz))) return rc;
+        std::vector<uint64_t> sb(W), rb(W);
+        for (int r = 0; r < W; ++r) {
+            sb[r] = size_of(me, r, a < NT ? 0 : 1) * esz;
+            rb[r] = size_of(r, me, a < NT ? 0 : 1) * esz;
+        }
+        if ((rc = pag_comm_all_to_all_v(R.c, g->pool[send_slot(a)].p, sb.data(), imp.p, rb.data()))) return rc;
+    }
+    R.region_books.xfer = R.clock.lap();
+    return PAG_OK;
+}
+
+// 5. the graph arrays are in the import slots: the handle takes them over with the sums of the owners' statistics
+int adopt_region(ShardRun &R, pag_build_stats *total) {
+    int rc;
+    pag_build_stats st{};
+    for (const pag_build_stats &p : R.from_owner) add_stats(st, p);
+    if ((rc = pag_shard_adopt(R.g, R.T, R.E, &st)) || (rc = pag_shard_set_region(R.g, &R.regions[R.me])) || (rc = pag_shard_release_build(R.g))) return rc;
+    if (total) *total = st;
+    return PAG_OK;
+}
+
+int shard_run(pag_graph *g, pag_comm *c, const pag_build_input *in, const pag_region *regions, pag_build_stats *total) {
+    ShardRun R{g, c, in, regions, c->world, c->rank, g->stream};
+    if (const char *e = std::getenv("PAG_SHARD_CHUNKS")) R.C = std::max(1, std::min(64, std::atoi(e)));
+    const bool pipeline = env_int("PAG_SHARD_PIPELINE", 1) != 0;
+    int rc;
+    uint64_t wire[2];  // payload out in the two bulk exchanges
+    const uint64_t sent0 = pag_comm_bytes_sent(c);
+    if ((rc = exchange_streams(R))) return rc;
+    wire[0] = pag_comm_bytes_sent(c) - sent0;
+    R.clock.lap();
+    if ((rc = lay_out_owned(R))) return rc;
+    R.s_layout = R.clock.lap();
+    if ((rc = build_owned(R))) return rc;
+    R.s_build = R.clock.lap();
+    if ((rc = reserve_send_buffers(R)) || (rc = pipeline ? exchange_regions_ring(R) : exchange_regions_whole(R))) return rc;
+    wire[1] = pag_comm_bytes_sent(c) - sent0 - wire[0];
+    if ((rc = adopt_region(R, total))) return rc;
+    R.s_adopt = R.clock.lap();
+    const OverlapBooks &tb = R.tuple_books, &rb = R.region_books;
+    if (R.clock.on)
+        std::fprintf(stderr,
+                     "[shard timing] rank %d/%d tuples in %d chunks: extraction + owner partition %.4f s, exchange %.4f s of which %.4f s beside the next chunk's "
+                     "extraction (loop %.4f s, %llu B out), owner layout %.4f s, K2-K4 %.4f s; regions %s: selections for %d ranks %.4f s, exchange %.4f s of which "
+                     "%.4f s beside the next selection (loop %.4f s, %llu B out), owner order %.4f s, import+region+release %.4f s\n",
+                     R.me, R.W, R.C, tb.step, tb.xfer, tb.hidden, tb.loop, (unsigned long long)wire[0], R.s_layout, R.s_build, pipeline ? "pipelined" : "whole", R.W,
+                     rb.step, rb.xfer, rb.hidden, rb.loop, (unsigned long long)wire[1], R.s_owner_order, R.s_adopt);
+    return PAG_OK;
+}
+}  // namespace
+
+extern "C" int pag_shard_run(pag_graph *g, pag_comm *c, const pag_build_input *in, const pag_region *regions, pag_build_stats *total) {
     if (!g || !c || !in || !regions) return PAG_EINVAL;
     const int rc = shard_run(g, c, in, regions, total);
     if (rc != PAG_OK) pag_comm_abort(c, pag_last_error());  // the peers learn why instead of waiting for this rank
     return rc;
 }
-static int shard_run(pag_graph *g, pag_comm *c, const pag_build_input *in, const pag_region *regions, pag_build_stats *total) {
-    using namespace pagdev;
-    const int W = c->world, me = c->rank;
-    int rc;
-    // PAG_SHARD_TIMING=1: one line per rank and block on stderr — seconds per stage of this call (the device idle at every
-    // boundary) and the payload that left the rank in each of the two bulk exchanges
-    const bool timing = env_timing();
-    double lap[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    uint64_t wire[2] = {0, 0};
-    auto now = [&]() {
-        if (timing) hipDeviceSynchronize();
-        return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-    };
-    double t_prev = now();
-    auto mark = [&](int i) {
-        if (!timing) return;
-        const double t = now();
-        lap[i] += t - t_prev;
-        t_prev = t;
-    };
-    // ---- extraction in CHUNKS, every chunk's partitioned streams on their way to the owners while the next chunk is extracted
-    //      (SURVEY.md 8e).  PAG_SHARD_CHUNKS (default 4; 1: the whole range at once).  A chunk's streams are copied out of the
-    //      extraction's slots (the next chunk overwrites them) and received into arrays of their own; when the last chunk has
-    //      arrived the owner lays the pieces out as [pass 1: rank 0 chunk 0, chunk 1 .. rank 1 ..][pass 2: ..] — the ranks' read
-    //      ranges and, inside a rank, its chunks are contiguous in emission order, so that is the canonical order again.
-    hipStream_t s = g->stream;
-    const uint64_t n_reads = in->reads.n_seqs, r_lo = n_reads * (uint64_t)me / (uint64_t)W, r_hi = n_reads * ((uint64_t)me + 1) / (uint64_t)W;
-    int C = 4;
-    if (const char *e = std::getenv("PAG_SHARD_CHUNKS")) C = std::max(1, std::min(64, std::atoi(e)));
-    std::vector<std::vector<uint64_t>> allc((size_t)C, std::vector<uint64_t>(4 * (size_t)W * W));
-    auto cnt = [&](int ch, int src, int dst, int q) { return allc[(size_t)ch][((size_t)src * W + dst) * 4 + q]; };
-    struct ChunkBufs {
-        void *send[4] = {nullptr, nullptr, nullptr, nullptr};  // tkey tval ekey eval of this rank's chunk, partitioned by owner
-        void *recv[4] = {nullptr, nullptr, nullptr, nullptr};  // what the ranks sent of theirs
-    };
-    std::vector<ChunkBufs> cb((size_t)C);
-    DevCall tmp("pag_shard_run"), sent("pag_shard_run");  // the chunks as received; this rank's copies of them on their way out
-    Xchg X;
-    XchgGuard xguard{X};
-    double t_extract = 0, t_xfer = 0, t_loop0 = 0, t_hidden = 0;
-    const uint64_t sent0 = pag_comm_bytes_sent(c);
-    {
-        const double tl0 = now_s();
-        double prev_begin = 0;
-        for (int ch = 0; ch < C; ++ch) {
-            const uint64_t lo = r_lo + (r_hi - r_lo) * (uint64_t)ch / (uint64_t)C, hi = r_lo + (r_hi - r_lo) * ((uint64_t)ch + 1) / (uint64_t)C;
-            std::vector<uint64_t> counts(4 * (size_t)W);
-            const double te0 = now_s();
-            if ((rc = pag_shard_extract_range(g, in, lo, hi, (uint32_t)W, counts.data()))) return rc;
-            const StreamPtrs part = streams_at(g, g->shard_in0[0], g->shard_in0[1]);
-            const uint64_t Tc = g->shard_x[0], Ec = g->shard_x[1];
-            const void *src[4] = {part.tkey, part.tval, part.ekey, part.eval};
-            for (int a = 0; a < 4; ++a) {
-                const uint64_t n = a < 2 ? Tc : Ec;
-                char *q = nullptr;
-                if ((rc = sent.alloc(&q, (n + 1) * ps::STREAM_ESZ[a]))) return rc;
-                cb[ch].send[a] = q;
-                if (n) PAG_HIP_TRY(hipMemcpyAsync(cb[ch].send[a], src[a], n * ps::STREAM_ESZ[a], hipMemcpyDeviceToDevice, s));
-            }
-            PAG_HIP_TRY(hipStreamSynchronize(s));
-            const double te1 = now_s();
-            t_extract += te1 - te0;
-            if ((rc = pag_comm_all_gather(c, counts.data(), counts.size() * 8, allc[(size_t)ch].data()))) return rc;
-            // the chunk before this one has been travelling beside this extraction
-            const bool was_active = X.active;
-            if ((rc = xchg_end(X))) return rc;
-            if (was_active) {
-                t_xfer += X.t_done - prev_begin;
-                t_hidden += std::max(0.0, std::min(X.t_done, te1) - std::max(prev_begin, te0));
-            }
-            std::vector<XchgArr> arrs(4);
-            for (int a = 0; a < 4; ++a) {
-                const int q0 = a < 2 ? 0 : 2;
-                uint64_t tot = 0;
-                arrs[a].sb.resize(W);
-                arrs[a].rb.resize(W);
-                for (int r = 0; r < W; ++r) {
-                    arrs[a].sb[r] = (cnt(ch, me, r, q0) + cnt(ch, me, r, q0 + 1)) * ps::STREAM_ESZ[a];
-                    arrs[a].rb[r] = (cnt(ch, r, me, q0) + cnt(ch, r, me, q0 + 1)) * ps::STREAM_ESZ[a];
-                    tot += arrs[a].rb[r];
-                }
-                char *q = nullptr;
-                if ((rc = tmp.alloc(&q, tot + ps::STREAM_ESZ[a]))) return rc;
-                cb[ch].recv[a] = q;
-                arrs[a].send = cb[ch].send[a];
-                arrs[a].recv = cb[ch].recv[a];
-            }
-            if ((rc = xchg_begin(c, X, std::move(arrs)))) return rc;
-            prev_begin = X.t_begin;
-        }
-        if ((rc = xchg_end(X))) return rc;
-        t_xfer += X.t_done - prev_begin;
-        t_loop0 = now_s() - tl0;
-    }
-    mark(0);
-    uint64_t nT = 0, nE = 0, t1 = 0, e1 = 0;
-    for (int ch = 0; ch < C; ++ch)
-        for (int r = 0; r < W; ++r) {
-            nT += cnt(ch, r, me, 0) + cnt(ch, r, me, 1);
-            nE += cnt(ch, r, me, 2) + cnt(ch, r, me, 3);
-            t1 += cnt(ch, r, me, 0);
-            e1 += cnt(ch, r, me, 2);
-        }
-    sent.release();  // (the chunks' send copies are done with)
-    DevBuf b_lk(g, ps::OWN_TK), b_lv(g, ps::OWN_TV), b_lek(g, ps::OWN_EK), b_lev(g, ps::OWN_EV);
-    if ((rc = b_lk.alloc((nT + 1) * 4)) || (rc = b_lv.alloc((nT + 1) * 8)) || (rc = b_lek.alloc((nE + 1) * 4)) || (rc = b_lev.alloc((nE + 1) * 8))) return rc;
-    mark(1);
-    {
-        // [pass 1 from rank 0: chunk 0, chunk 1 ..] .. [pass 1 from rank W-1 ..] [pass 2 from rank 0 ..] ..; a chunk's received array
-        // is [from rank 0: pass 1, pass 2][from rank 1: ..]
-        void *dst_of[4] = {b_lk.p, b_lv.p, b_lek.p, b_lev.p};
-        for (int a = 0; a < 4; ++a) {
-            const int q0 = a < 2 ? 0 : 2;
-            std::vector<uint64_t> src_at((size_t)C, 0);  // read position in every chunk's received array
-            uint64_t d1 = 0, d2 = a < 2 ? t1 : e1;
-            for (int r = 0; r < W; ++r)
-                for (int ch = 0; ch < C; ++ch) {
-                    const uint64_t p1 = cnt(ch, r, me, q0), p2 = cnt(ch, r, me, q0 + 1);
-                    const char *from = (const char *)cb[ch].recv[a] + src_at[(size_t)ch] * ps::STREAM_ESZ[a];
-                    if (p1) PAG_HIP_TRY(hipMemcpyAsync((char *)dst_of[a] + d1 * ps::STREAM_ESZ[a], from, p1 * ps::STREAM_ESZ[a], hipMemcpyDeviceToDevice, s));
-                    if (p2) PAG_HIP_TRY(hipMemcpyAsync((char *)dst_of[a] + d2 * ps::STREAM_ESZ[a], from + p1 * ps::STREAM_ESZ[a], p2 * ps::STREAM_ESZ[a], hipMemcpyDeviceToDevice, s));
-                    src_at[(size_t)ch] += p1 + p2;
-                    d1 += p1;
-                    d2 += p2;
-                }
-        }
-        PAG_HIP_TRY(hipStreamSynchronize(s));
-    }
-    tmp.release();
-    mark(2);
-    wire[0] = pag_comm_bytes_sent(c) - sent0;
-    pag_build_stats mine{};
-    if ((rc = pag_shard_build(g, b_lk.as<uint32_t>(), b_lv.as<uint64_t>(), nT, t1, b_lek.as<uint32_t>(), b_lev.as<uint64_t>(), nE, e1, in->eps, &mine))) return rc;
-    mark(3);
-    // ---- every rank's region of this owner's slice
-    std::vector<pag_shard_slice> sel(W);
-    std::vector<uint64_t> my_sizes(2 * (size_t)W), all_sizes(2 * (size_t)W * W);
-    // (a selection lives in the handle until the next one: copied behind the previous ones into the send buffers)
-    constexpr int NA = ps::GRAPH_ARRS, NT = ps::GRAPH_TUPLE_ARRS;  // the seven arrays of a graph, the first four per tuple
-    const int *const esz = ps::GRAPH_ESZ;
-    auto send_slot = [](int a) { return ps::family(ps::SEND, a); };  // the send buffers
-    std::vector<uint64_t> at(NA, 0);
-    std::vector<pag_build_stats> stats_to(W);
-    // the send buffers are sized once for what the selections of all destinations usually add up to — the slice itself plus
-    // the landing zones and halos that several ranks take (1.2x at N = 4, measured) — so that the loop below neither
-    // allocates nor copies what it has already gathered; a block that needs more grows them as before
-    for (int a = 0; a < NA; ++a) {
-        const uint64_t n_slice = a < NT ? g->n_t : g->n_e;
-        DevBuf b(g, send_slot(a));
-        if ((rc = b.alloc((n_slice + n_slice / 2 + 1024) * esz[a]))) return rc;
-    }
-    // (PAG_SHARD_PIPELINE=0: all selections first, then seven whole all-to-all(v)s, as until round 5)
-    const bool pipeline = env_int("PAG_SHARD_PIPELINE", 1) != 0;
-    uint64_t T = 0, E = 0;
-    std::vector<pag_build_stats> from_owner(W);  // the statistics of what owner o selected for this rank
-    DevBuf imp[NA];
-    for (int a = 0; a < NA; ++a) imp[a] = DevBuf(g, ps::family(ps::IMPORT, a));
-    double t_select = 0, t_rxfer = 0, t_rhidden = 0, t_loop1 = 0;
-    const uint64_t sent1 = pag_comm_bytes_sent(c);
-    if (pipeline) {
-        // Step i: this owner selects the region of rank (me + i) mod W and receives, from rank (me - i) mod W, that owner's
-        // selection for this rank; the selection of step i travels while the one of step i + 1 is made.  What arrives is kept
-        // per owner and put in owner order (ascending k-mer ranges) when the last piece is there.
-        struct StepMsg {
-            uint64_t n_t, n_e;
-            pag_build_stats st;
-        };
-        std::vector<std::vector<void *>> piece((size_t)W, std::vector<void *>(NA, nullptr));  // [owner][array]
-        std::vector<uint64_t> piece_t(W, 0), piece_e(W, 0);
-        DevCall rtmp("pag_shard_run");
-        Xchg X;
-        XchgGuard xguard{X};
-        const double tl0 = now_s();
-        double prev_begin = 0;
-        for (int i = 0; i < W; ++i) {
-            const int dst = (me + i) % W, src = (me - i + W) % W;
-            const double ts0 = now_s();
-            if ((rc = pag_shard_select(g, &regions[dst], &sel[dst]))) return rc;
-            const GraphArrays from = arrays_of(sel[dst]);
-            std::vector<uint64_t> at0 = at;
-            for (int a = 0; a < NA; ++a) {
-                const uint64_t n = a < NT ? sel[dst].n_t : sel[dst].n_e;
-                DevBuf b(g, send_slot(a));
-                const uint64_t need = (at[a] + n + 1) * esz[a];
-                if (b.sl->cap < need) {
-                    // (grown with the old contents kept; an exchange that still reads the old array is waited for first)
-                    if ((rc = xchg_end(X)) || (rc = b.alloc_keeping(need, at[a] * esz[a], need + need / 2 + 256))) return rc;
-                    if (piece[(size_t)me][a]) piece[(size_t)me][a] = b.sl->p;  // (this rank's own piece lies at the front of these arrays)
-                }
-                if (n) PAG_HIP_TRY(hipMemcpyAsync((char *)b.sl->p + at[a] * esz[a], from.p[a], n * esz[a], hipMemcpyDeviceToDevice, s));
-                at[a] += n;
-            }
-            PAG_HIP_TRY(hipStreamSynchronize(s));
-            const double ts1 = now_s();
-            t_select += ts1 - ts0;
-            std::vector<StepMsg> msg(W);
-            StepMsg mine_msg{sel[dst].n_t, sel[dst].n_e, sel[dst].stats};
-            if ((rc = pag_comm_all_gather(c, &mine_msg, sizeof mine_msg, msg.data()))) return rc;
-            const bool was_active = X.active;
-            if ((rc = xchg_end(X))) return rc;
-            if (was_active) {
-                t_rxfer += X.t_done - prev_begin;
-                t_rhidden += std::max(0.0, std::min(X.t_done, ts1) - std::max(prev_begin, ts0));
-            }
-            piece_t[(size_t)src] = msg[(size_t)src].n_t;
-            piece_e[(size_t)src] = msg[(size_t)src].n_e;
-            from_owner[(size_t)src] = msg[(size_t)src].st;
-            if (i == 0) {  // this rank's own selection stays where it is
-                for (int a = 0; a < NA; ++a) piece[(size_t)me][a] = (char *)g->pool[send_slot(a)].p + at0[a] * esz[a];
-                continue;
-            }
-            std::vector<XchgArr> xa(NA);
-            for (int a = 0; a < NA; ++a) {
-                const uint64_t n_out = a < NT ? sel[dst].n_t : sel[dst].n_e, n_in = a < NT ? piece_t[(size_t)src] : piece_e[(size_t)src];
-                char *q = nullptr;
-                if ((rc = rtmp.alloc(&q, (n_in + 1) * esz[a]))) return rc;
-                piece[(size_t)src][a] = q;
-                xa[a].sb.assign(W, 0);
-                xa[a].rb.assign(W, 0);
-                xa[a].sb[(size_t)dst] = n_out * esz[a];
-                xa[a].rb[(size_t)src] = n_in * esz[a];
-                xa[a].send = (const char *)g->pool[send_slot(a)].p + at0[a] * esz[a];
-                xa[a].recv = piece[(size_t)src][a];
-            }
-            if ((rc = xchg_begin(c, X, std::move(xa)))) return rc;
-            prev_begin = X.t_begin;
-        }
-        const bool was_active = X.active;
-        if ((rc = xchg_end(X))) return rc;
-        if (was_active) t_rxfer += X.t_done - prev_begin;
-        t_loop1 = now_s() - tl0;
-        mark(4);
-        for (int o = 0; o < W; ++o) {
-            T += piece_t[(size_t)o];
-            E += piece_e[(size_t)o];
-        }
-        for (int a = 0; a < NA; ++a) {
-            if ((rc = imp[a].alloc(((a < NT ? T : E) + 1) * esz[a]))) return rc;
-            uint64_t off = 0;
-            for (int o = 0; o < W; ++o) {  // owner order = ascending k-mer ranges
-                const uint64_t n = a < NT ? piece_t[(size_t)o] : piece_e[(size_t)o];
-                if (n) PAG_HIP_TRY(hipMemcpyAsync((char *)imp[a].p + off * esz[a], piece[(size_t)o][a], n * esz[a], hipMemcpyDeviceToDevice, s));
-                off += n;
-            }
-        }
-        PAG_HIP_TRY(hipStreamSynchronize(s));
-    } else {
-    for (int d = 0; d < W; ++d) {
-        if ((rc = pag_shard_select(g, &regions[d], &sel[d]))) return rc;
-        my_sizes[2 * d] = sel[d].n_t;
-        my_sizes[2 * d + 1] = sel[d].n_e;
-        stats_to[d] = sel[d].stats;
-        const GraphArrays src = arrays_of(sel[d]);
-        for (int a = 0; a < NA; ++a) {
-            const uint64_t n = a < NT ? sel[d].n_t : sel[d].n_e;
-            DevBuf b(g, send_slot(a));
-            // (grown with the old contents kept)
-            const uint64_t need = (at[a] + n + 1) * esz[a];
-            if ((rc = b.alloc_keeping(need, at[a] * esz[a], need + need / 2 + 256))) return rc;
-            if (n) PAG_HIP_TRY(hipMemcpyAsync((char *)b.sl->p + at[a] * esz[a], src.p[a], n * esz[a], hipMemcpyDeviceToDevice, s));
-            at[a] += n;
-        }
-        PAG_HIP_TRY(hipStreamSynchronize(s));
-    }
-    mark(4);
-    if ((rc = pag_comm_all_gather(c, my_sizes.data(), my_sizes.size() * 8, all_sizes.data()))) return rc;
-    std::vector<pag_build_stats> all_stats((size_t)W * W);
-    if ((rc = pag_comm_all_gather(c, stats_to.data(), stats_to.size() * sizeof(pag_build_stats), all_stats.data()))) return rc;
-    auto size_of = [&](int owner, int dst, int which) { return all_sizes[((size_t)owner * W + dst) * 2 + which]; };
-    for (int o = 0; o < W; ++o) {
-        T += size_of(o, me, 0);
-        E += size_of(o, me, 1);
-    }
-    // received straight into the buffers pag_shard_import fills (ps::IMPORT): owner order = ascending k-mer ranges
-    for (int a = 0; a < NA; ++a) {
-        const uint64_t n = a < NT ? T : E;
-        if ((rc = imp[a].alloc((n + 1) * esz[a]))) return rc;
-        std::vector<uint64_t> sb(W), rb(W);
-        for (int r = 0; r < W; ++r) {
-            sb[r] = size_of(me, r, a < NT ? 0 : 1) * esz[a];
-            rb[r] = size_of(r, me, a < NT ? 0 : 1) * esz[a];
-        }
-        if ((rc = pag_comm_all_to_all_v(c, g->pool[send_slot(a)].p, sb.data(), imp[a].p, rb.data()))) return rc;
-    }
-        for (int o = 0; o < W; ++o) from_owner[(size_t)o] = all_stats[(size_t)o * W + me];
-    }
-    mark(5);
-    wire[1] = pag_comm_bytes_sent(c) - sent1;
-    pag_build_stats st{};
-    for (int o = 0; o < W; ++o) {
-        const pag_build_stats &P = from_owner[(size_t)o];
-        for (int q = 0; q < 2; ++q) {
-            st.merge_edge[q] += P.merge_edge[q];
-            st.total_pos[q] += P.total_pos[q];
-            st.merge_pos[q] += P.merge_pos[q];
-            st.n_tuples[q] += P.n_tuples[q];
-            st.n_edges[q] += P.n_edges[q];
-        }
-        st.n_nodes += P.n_nodes;
-        st.n_pos += P.n_pos;
-        st.n_uniq_edges += P.n_uniq_edges;
-    }
-    if ((rc = pag_shard_adopt(g, T, E, &st))) return rc;
-    if ((rc = pag_shard_set_region(g, &regions[me]))) return rc;
-    if ((rc = pag_shard_release_build(g))) return rc;
-    mark(6);
-    if (timing)
-        std::fprintf(stderr,
-                     "[shard timing] rank %d/%d tuples in %d chunks: extraction + owner partition %.4f s, exchange %.4f s of which %.4f s beside the next chunk's "
-                     "extraction (loop %.4f s, %llu B out), owner layout %.4f s, K2-K4 %.4f s; regions %s: selections for %d ranks %.4f s, exchange %.4f s of which "
-                     "%.4f s beside the next selection (loop %.4f s, %llu B out), owner order %.4f s, import+region+release %.4f s\n",
-                     me, W, C, t_extract, t_xfer, t_hidden, t_loop0, (unsigned long long)wire[0], lap[1] + lap[2], lap[3], pipeline ? "pipelined" : "whole", W,
-                     pipeline ? t_select : lap[4], pipeline ? t_rxfer : lap[5], t_rhidden, t_loop1, (unsigned long long)wire[1], pipeline ? lap[5] : 0.0, lap[6]);
-    if (total) *total = st;
-    return PAG_OK;
-}
 
-}  // extern "C"

@@ -18,7 +18,6 @@
 // went, while the allocations of a turn are one set of build slots and one set of traversal slots, not one per owner.  The
 // pinned path memory, the walk streams and the import family stay from turn to turn.
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -30,8 +29,6 @@
 using namespace pagdev;
 
 namespace {
-
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // what the traversal of the turn before took: its slots (graph view, successor records, walk session) and the walk arena, which
 // pag_travel sizes again from what is free once the build is released (as it did for the prototype's fresh handles)
@@ -64,19 +61,6 @@ void release_build_keeping(pag_graph *g, const pag_build_input *in) {
         for (const void *p : keep) used = used || (p && (const char *)p >= lo && (const char *)p < hi);
         if (!used) slot_free(g, sl);
     }
-}
-
-void add_stats(pag_build_stats &st, const pag_build_stats &p) {
-    for (int q = 0; q < 2; ++q) {
-        st.merge_edge[q] += p.merge_edge[q];
-        st.total_pos[q] += p.total_pos[q];
-        st.merge_pos[q] += p.merge_pos[q];
-        st.n_tuples[q] += p.n_tuples[q];
-        st.n_edges[q] += p.n_edges[q];
-    }
-    st.n_nodes += p.n_nodes;
-    st.n_pos += p.n_pos;
-    st.n_uniq_edges += p.n_uniq_edges;
 }
 
 bool same_count_lines(const pag_build_stats &a, const pag_build_stats &b) {
@@ -124,14 +108,14 @@ int serial_turn(pag_graph *g, const pag_build_input *in, const pag_region *regio
     std::vector<uint64_t> full((size_t)4 * n);
     for (uint32_t o = 0; o < n; ++o) {
         t0 = now_s();
-        const OwnerLayout L = owner_layout(S.counts.data(), n, o);
+        const OwnerLayout L = owner_layout(S.counts.data(), n, n, o);
         DevBuf own_tk(g, ps::OWN_TK), own_tv(g, ps::OWN_TV), own_ek(g, ps::OWN_EK), own_ev(g, ps::OWN_EV);
         if ((rc = own_tk.alloc((L.n_t + 1) * 4)) || (rc = own_tv.alloc((L.n_t + 1) * 8)) || (rc = own_ek.alloc((L.n_e + 1) * 4)) ||
             (rc = own_ev.alloc((L.n_e + 1) * 8)))
             return rc;
         for (uint32_t r = 0; r < n; ++r) {
             const uint64_t *first = S.counts.data() + ((size_t)r * n + o) * 4;
-            const RangeSlots at = range_slots(S.counts.data(), n, o, r);
+            const RangeSlots at = range_slots(S.counts.data(), n, n, o, r);
             uint64_t c[4] = {0, 0, 0, 0};
             if (!via_partition) {
                 if ((rc = pag_shard_extract_for(g, in, range_lo(r), range_lo(r + 1), n, o, own_tk.as<uint32_t>(), own_tv.as<uint64_t>(), L.n_t, at.t_at1,

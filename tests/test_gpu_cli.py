@@ -190,9 +190,13 @@ def test_one_block_built_by_several_pagraph_processes(name, world, workdir):
 @pytest.mark.gpu
 @pytest.mark.parametrize("label,world,extra", [
     ("whole exchanges", 2, {"PAG_SHARD_CHUNKS": "1", "PAG_SHARD_PIPELINE": "0"}),
+    ("whole exchanges, four ranks", 4, {"PAG_SHARD_CHUNKS": "1", "PAG_SHARD_PIPELINE": "0"}),
     ("three chunks", 4, {"PAG_SHARD_CHUNKS": "3"}),
     ("more chunks than a rank has reads", 2, {"PAG_SHARD_CHUNKS": "64"}),
     ("one rank over RCCL with itself", 1, {"PAG_COMM_FORCE_RCCL": "1", "PAGRAPH_SHARD_TRANSPORT": "rccl"}),
+    # (four ranks: with two, an error in the by-owner offsets of ranks 1 .. W - 2 cannot show — whole exchanges above, and here
+    # the whole region exchange behind CHUNKED tuples)
+    ("three chunks, whole region exchange, four ranks", 4, {"PAG_SHARD_CHUNKS": "3", "PAG_SHARD_PIPELINE": "0"}),
 ])
 def test_sharded_build_in_chunks_and_pipelined_equals_the_golden(label, world, extra, workdir):
     """pag_shard_run sends a rank's tuples in chunks while the next chunk is extracted, and the selection for one rank while the

@@ -4,7 +4,8 @@
 counts[r][o] = (tuples pass 1, tuples pass 2, edges pass 1, edges pass 2) that read range r sends owner o.  The expected
 values are a second restatement, written here from the definition in include/pagraph_hip.h (pag_shard_*): an owner builds from
 [pass 1 from range 0] .. [pass 1 from range N-1] [pass 2 from range 0] ..; a range's partitioned stream is, owners ascending,
-[its pass-1 records][its pass-2 records].  The same cases run once more as a program of its own under the address and
+[its pass-1 records][its pass-2 records].  The chunks of the ranks of a sharded build (pag_shard_run) are such ranges, rank-major:
+the copy plan of a chunked receive is executed on labelled records and held against that order.  The same cases run once more as a program of its own under the address and
 undefined-behaviour sanitizers (tests/harness/serial_layout_main.cpp: host code, nothing loaded into Python)."""
 import ctypes as C
 import os
@@ -27,6 +28,8 @@ def lib():
     L.pagt_owner_layout.argtypes = [P, u32, u32, P]
     L.pagt_range_slots.argtypes = [P, u32, u32, u32, P]
     L.pagt_partitioned_slots.argtypes = [P, u32, u32, u32, P]
+    L.pagt_chunked_receive_plan.argtypes = [P, u32, u32, u32, u32, P, P, C.c_uint64]
+    L.pagt_chunked_receive_plan.restype = C.c_uint64
     return L
 
 
@@ -97,6 +100,94 @@ def test_stretches_tile_the_owner_buffers(lib, n):
                     at, c = got[2 * stream + ps], int(counts[r, o, 2 * stream + ps])
                     seen[at:at + c] += 1
             assert (seen == 1).all()
+
+
+# ---- the copy plan of a chunked receive (pag_shard_run): counts[rank, chunk, owner] = the four counts of that chunk for that owner.
+# The chunks of the ranks, rank-major, are the ranges of the rule above; a chunk's receive array is, as the exchange fills it,
+# [from rank 0: pass 1, pass 2][from rank 1: ..].
+
+
+def receive_plan(lib, counts, o, stream):
+    """(n, n1, [(chunk, source offset, destination offset, count)]) of owner o's tuples (stream 0) or edges (1)"""
+    W, Cn = counts.shape[:2]
+    flat = np.ascontiguousarray(counts, dtype=np.uint64)
+    sizes, cap = (C.c_uint64 * 2)(), 2 * W * Cn  # (at most one copy per rank, chunk and pass)
+    copies = np.zeros((cap, 4), dtype=np.uint64)
+    k = lib.pagt_chunked_receive_plan(flat.ctypes.data, W, Cn, o, stream, sizes, copies.ctypes.data, cap)
+    assert k <= cap
+    return int(sizes[0]), int(sizes[1]), [tuple(int(v) for v in row) for row in copies[:k]]
+
+
+def chunk_counts(W, Cn, draw):
+    """counts from 0..5, at least a third of them zero.  Draw 0 takes the conditions to the letter — an empty chunk for every rank
+    ("more chunks than a rank has reads"), one rank that sends nothing — which leaves nothing at all where C = 1 or W = 1; the
+    draws after it apply each condition where something is left beside it."""
+    rng = np.random.default_rng(1000 * W + 10 * Cn + draw)
+    c = rng.integers(0, 6, size=(W, Cn, W, 4)).astype(np.uint64)
+    c[rng.random(c.shape) < 0.3] = 0
+    if draw == 0 or Cn > 1:
+        for rank in range(W):
+            c[rank, rng.integers(Cn)] = 0
+    if draw == 0 or W > 1:
+        c[rng.integers(W)] = 0
+    flat = c.reshape(-1)
+    while (flat == 0).sum() * 3 < flat.size:
+        flat[rng.integers(flat.size)] = 0
+    return c
+
+
+@pytest.mark.parametrize("Cn", [1, 3, 4, 64])
+@pytest.mark.parametrize("W", [1, 2, 4, 8])
+def test_the_chunked_receive_plan_executed_on_labels_gives_the_owners_order(lib, W, Cn):
+    """every record labelled (rank, chunk, pass, index), the chunks' receive arrays laid out as the exchange fills them, the plan
+    executed on the labels: the canonical order written down directly, every source and destination record touched exactly once"""
+    for draw in range(3):
+        counts = chunk_counts(W, Cn, draw)
+        assert (counts == 0).sum() * 3 >= counts.size
+        if draw == 0 or Cn > 1:
+            assert all((counts[rank].sum(axis=(1, 2)) == 0).any() for rank in range(W)), "an empty chunk for every rank"
+        if draw == 0 or W > 1:
+            assert (counts.sum(axis=(1, 2, 3)) == 0).any(), "a rank that sends the owner nothing"
+        for o in range(W):
+            for stream in (0, 1):
+                def labels(rank, ch, ps):
+                    return [(rank, ch, ps, i) for i in range(int(counts[rank, ch, o, 2 * stream + ps]))]
+                recv = [[x for rank in range(W) for ps in (0, 1) for x in labels(rank, ch, ps)] for ch in range(Cn)]
+                want = [x for ps in (0, 1) for rank in range(W) for ch in range(Cn) for x in labels(rank, ch, ps)]
+                n, n1, copies = receive_plan(lib, counts, o, stream)
+                where = f"W = {W}, C = {Cn}, draw {draw}, owner {o}, stream {stream}"
+                assert (n, n1) == (len(want), sum(x[2] == 0 for x in want)), where
+                got, taken = [None] * n, [[0] * len(a) for a in recv]
+                for chunk, src, dst, cnt in copies:
+                    assert cnt > 0 and chunk < Cn and src + cnt <= len(recv[chunk]) and dst + cnt <= n, where
+                    for i in range(cnt):
+                        assert got[dst + i] is None, where + ": a destination record written twice"
+                        got[dst + i] = recv[chunk][src + i]
+                        taken[chunk][src + i] += 1
+                assert got == want, where
+                assert all(t == 1 for a in taken for t in a), where + ": a source record not copied exactly once"
+
+
+def test_the_chunked_receive_plan_is_exact_beyond_32_and_35_bits(lib):
+    """per-entry counts around 2^33: only the plan's arithmetic, against Python's integers; no record is touched"""
+    W, Cn = 8, 64
+    rng = np.random.default_rng(33)
+    counts = ((1 << 33) + rng.integers(-1000, 1000, size=(W, Cn, W, 4))).astype(np.uint64)
+    for o in (0, W - 1):
+        for stream in (0, 1):
+            cnt = [[[int(counts[rank, ch, o, 2 * stream + ps]) for ps in (0, 1)] for ch in range(Cn)] for rank in range(W)]
+            total = [sum(cnt[rank][ch][ps] for rank in range(W) for ch in range(Cn)) for ps in (0, 1)]
+            n, n1, copies = receive_plan(lib, counts, o, stream)
+            assert (n, n1) == (total[0] + total[1], total[0]) and n > 1 << 35
+            want, dst, src = [], [0, total[0]], [0] * Cn
+            for rank in range(W):
+                for ch in range(Cn):
+                    for ps in (0, 1):
+                        want.append((ch, src[ch], dst[ps], cnt[rank][ch][ps]))
+                        src[ch] += cnt[rank][ch][ps]
+                        dst[ps] += cnt[rank][ch][ps]
+            assert copies == want
+            assert max(c[1] for c in copies) > 1 << 35 and max(c[2] for c in copies) > 1 << 35
 
 
 def test_the_same_cases_under_the_sanitizers():
